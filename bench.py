@@ -7,14 +7,18 @@ Workload: SmolLM-1.7B geometry, 15 layers, seq 1024, micro-batch 4, grad_acc 32 
 reference README / config 3 per-GPU workload; weak scaling over DP), bf16, random init with the
 reference's init procedure, synthetic uniform tokens already resident on the GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--grad-acc G] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--grad-acc G] [--dump-outputs DIR] [--full]
 For N > 1 the driver launches one process per GPU with torch.distributed.run (`python bench.py --gpus N`
 without that launcher starts it itself, before touching the GPU); DP gradients are all-reduced over RCCL
 (xGMI) by DataParallelBucket.
 
-Rank 0 prints ONE JSON line with `value` = whole-job tokens/s, a `roofline` object for the
-dominant kernel (timed live with HIP events on its own launch stream) and a `cpu_baseline` object
-(the oracle's CPU restatement of the same step on a bounded sample, rank 0 at N=1 only).
+Rank 0 prints ONE JSON line with `value` = whole-job tokens/s and `ms_per_step`. A plain run does only what
+that figure needs: set-up, the warm-up steps, the K timed steps, the line. `--dump-outputs DIR` also writes what
+the last timed step computed (dump_outputs below). `--full` adds everything else the benchmark measures, in runs
+of their own around the timed region: a `cpu_baseline` object (the oracle's CPU restatement of the same step on a
+bounded sample, rank 0 at N=1 only; --no-cpu-baseline leaves it out), the `kernels` table and a `roofline` object
+for the dominant kernel (timed live with HIP events on its own launch stream; --no-kernel-timing leaves them out)
+and, under DataParallelBucket, the `allreduce` object (exposed all-reduce time, bus bandwidth at N > 1).
 """
 import argparse
 import json
@@ -134,6 +138,34 @@ def setup(layers, grad_acc, world, device, optimizer="pico", fused_adam=True, po
     return cfg, model, opt, loader, num_params
 
 
+DUMP_SEED, DUMP_ELEMS, DUMP_BUDGET = 20240229, 32768, 6_000_000
+
+
+def dump_outputs(out_dir, losses, model):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32/float64 .npy files —
+    `loss.npy` (the loss every timed step returned, float64, the last step's last) and, per parameter, the gradient
+    the last step's micro-batches accumulated (`grad.<name>.npy`) and the weight after its optimizer step
+    (`param.<name>.npy`). A tensor of more than DUMP_ELEMS elements is sampled at DUMP_ELEMS flat indices drawn
+    from a generator seeded by DUMP_SEED and the parameter's position (the same indices in every run and build);
+    the sample shrinks so that weights and gradients stay within DUMP_BUDGET elements each (24 MB, 48 MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(losses, dtype=np.float64))
+    named = list(getattr(model, "module", model).named_parameters())
+    k = max(1, min(DUMP_ELEMS, DUMP_BUDGET // max(1, len(named))))
+    for i, (name, p) in enumerate(named):
+        idx = None
+        if p.numel() > k:
+            idx = torch.randint(p.numel(), (k,), generator=torch.Generator().manual_seed(DUMP_SEED + i)).to(p.device)
+        grad = p.grad if p.grad is not None else getattr(p, "main_grad", None)
+        for kind, t in (("param", p.detach()), ("grad", grad)):
+            if t is None:
+                continue
+            flat = t.reshape(-1)
+            flat = flat if idx is None else flat[idx]
+            np.save(os.path.join(out_dir, f"{kind}.{name}.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -141,11 +173,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--grad-acc", type=int, default=32)
     ap.add_argument("--layers", type=int, default=LAYERS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the per-kernel "
+                         "timings and roofline, the DP all-reduce exposure and bus bandwidth")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--backend", default="nccl",
                     help="process-group backend: nccl (= RCCL over xGMI, the product) or gloo (tests: several "
                          "ranks sharing one GPU, which RCCL refuses)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the kernels table and roofline")
     ap.add_argument("--sync-steps", action="store_true",
                     help="read the loss on the host after every step (one device sync per step, as a per-step "
                          "log line would) instead of once after the timed region")
@@ -179,7 +216,7 @@ def main():
     # CPU baseline first, before this process touches the GPU (its gloo ranks are fresh processes):
     # BASELINE.md's CPU plan, DP = 2 x 4 threads, SmolLM-1.7B geometry 2 layers, seq 1024 (oracle/cpu_baseline.py)
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.cpu_baseline import c1_cpu_throughput, dp2_cpu_throughput
         t0 = time.time()
         cpu_baseline = dp2_cpu_throughput()
@@ -221,8 +258,9 @@ def main():
                   L.K_RMSNORM_DW, L.K_ROPE, L.K_SWIGLU_FWD, L.K_SWIGLU_BWD, L.K_GRAD_ACCUM, L.K_CAST]
     # Per-launch HIP events cannot ride inside a graph replay, so with graphs the kernels are timed
     # over one extra eagerly launched step right after the timed region (same shapes, same stream).
+    kernel_timing = args.full and not args.no_kernel_timing
     kernel_timing_live = not args.graphs
-    if not args.no_kernel_timing and kernel_timing_live:
+    if kernel_timing and kernel_timing_live:
         cap = args.steps * args.grad_acc * (args.layers * 4 + 8) + 16
         for k in kernel_ids:
             L.prof_enable(k, cap)
@@ -245,9 +283,11 @@ def main():
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # before the untimed extra steps below touch the gradients and weights
+        dump_outputs(args.dump_outputs, losses, model)
 
     kernels = {}
-    if not args.no_kernel_timing and not kernel_timing_live:
+    if kernel_timing and not kernel_timing_live:
         cap = args.grad_acc * (args.layers * 4 + 8) + 16
         for k in kernel_ids:
             L.prof_enable(k, cap)
@@ -256,7 +296,7 @@ def main():
         torch.cuda.synchronize()
         if hasattr(model, "reset"):  # as TrainingStep.reset: the syncing micro-batch left every bucket marked ready
             model.reset()
-    if not args.no_kernel_timing:
+    if kernel_timing:
         for k in kernel_ids:
             tot, n = L.prof_collect(k)
             if n:
@@ -269,7 +309,7 @@ def main():
     # The steps run on every backend (the gloo tests exercise the same sequence as the RCCL run: kernel-timing step,
     # then these); only RCCL's timings are reported.
     exposure = None
-    if hasattr(model, "comm_timing") and args.comm_steps > 0:
+    if args.full and hasattr(model, "comm_timing") and args.comm_steps > 0:
         model.comm_timing(True)
         for _ in range(args.comm_steps):
             step(sync_loss=True)
@@ -280,7 +320,7 @@ def main():
             exposure = comm_exposure(report, world, device)
         else:
             exposure = {"exposed_ms": None, "exposed_over": f"not measured: {dist.get_backend()} backend"}
-    allreduce = measure_allreduce(model, world, device) if world > 1 else None
+    allreduce = measure_allreduce(model, world, device) if args.full and world > 1 else None
     if exposure is not None:
         allreduce = dict(allreduce or {"buckets": len(model.bucket_manager.buckets)}, **exposure)
 

@@ -615,7 +615,7 @@ def test_bench_dp2_gloo_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--layers", "2",
-           "--grad-acc", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--grad-acc", "3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -641,7 +641,7 @@ def test_bench_dp_bucket_grad_acc1_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dp-bucket", "--layers", "2", "--grad-acc", "1",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timing"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-kernel-timing"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -650,6 +650,42 @@ def test_bench_dp_bucket_grad_acc1_rccl():
     # measured over the untimed step(s) after the throughput region (bench --comm-steps), plus the W = 8 model
     assert ar["exposed_ms"] >= 0 and ar["buckets"] == len(ar["bucket_bytes"])
     assert set(ar["model_exposed_ms"]) == {"300.0", "600.0", "1071.0"}
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and reports nothing that needs a run of its own
+    (no kernels table, roofline, CPU baseline or all-reduce object); --dump-outputs writes the last step's loss,
+    gradients and updated weights as float32/float64 .npy files of at most 64 MB in all."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--layers", "2", "--grad-acc", "2",
+           "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)]
+    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["unit"] == "tokens/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    # value = tokens of the timed steps / their time (ms_per_step is rounded to 0.01 ms)
+    assert out["value"] == pytest.approx(4 * 1024 * 2 / (out["ms_per_step"] * 1e-3), rel=1e-3)
+    assert not out["kernels"] and out["roofline"] is None and out["cpu_baseline"] is None and out["allreduce"] is None
+    files = sorted(os.listdir(out_dir))
+    arrays = {f: np.load(out_dir / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    loss = arrays["loss.npy"]
+    assert loss.shape == (3,) and loss[-1] == pytest.approx(out["loss_last"], abs=1e-4)
+    params = [f for f in files if f.startswith("param.")]
+    assert params and [f.replace("param.", "grad.", 1) for f in params] == [f for f in files if f.startswith("grad.")]
+    assert all(np.isfinite(a).all() for a in arrays.values())
+    # the step trained: some gradient and some weight of the last step is non-zero
+    assert any(np.abs(arrays[f]).max() > 0 for f in files if f.startswith("grad."))
 
 
 def test_smollm_step_pipelined_paired_matches_eager(monkeypatch):
