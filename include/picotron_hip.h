@@ -24,6 +24,10 @@
  *   pico_cross_entropy_fwd/_bwd <- F.cross_entropy(logits, target, reduction='mean')
  *                                 (ref train.py:46-49, picotron/pipeline_parallel/pipeline_parallel.py:68,98)
  *   pico_adamw_bf16           <- torch.optim.AdamW(..., fused=True).step() (ref train.py:204-209,235)
+ *   pico_grad_sqnorm / _clip_coef / _scale, pico_adamw_bf16_clip
+ *                             <- torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm): no reference call
+ *                                 (the reference trains unclipped); what a Llama pre-training recipe adds between
+ *                                 the last backward and optimizer.step() (ref train.py:235)
  *   pico_sort_ids             <- the stable id sort inside F.embedding's backward (ref picotron/model.py:223-224)
  *   pico_embedding_bwd        <- backward of F.embedding (ref picotron/model.py:223-224) + the micro-batch
  *                                 gradient accumulation (data_parallel.py:131 / autograd's grad += dW)
@@ -73,7 +77,9 @@ enum {
   PICO_K_ADAMW = 21,
   PICO_K_ATTN_BWD_KV = 22, /* split backward: dK/dV key-major kernel */
   PICO_K_ATTN_BWD_Q = 23,  /* split backward: dQ query-major kernel (+ delta, LSE*log2e) */
-  PICO_K_COUNT = 24
+  PICO_K_GRAD_SQNORM = 24, /* global gradient norm: the per-chunk sum-of-squares kernel */
+  PICO_K_GRAD_SCALE = 25,  /* standalone gradient clip (pico_adamw_bf16_clip is timed under PICO_K_ADAMW) */
+  PICO_K_COUNT = 26
 };
 
 int pico_abi_version(void);
@@ -263,6 +269,32 @@ int64_t pico_adamw_chunk_elems(void);
 int pico_adamw_bf16(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
                     double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                     void* stream);
+
+/* ---- global L2 gradient norm and clip over a whole parameter list, on pico_adamw_bf16's device tables ----
+ * Replaces torch.nn.utils.clip_grad_norm_(params, max_norm) (norm_type 2). Only the grad and grad_is_f32 columns
+ * of `tensors` are read; an fp32 main_grad element counts as bf16(g), the value the deferred cast would store.
+ * pico_grad_sqnorm: one launch writes one fp32 partial sum of squares per chunk into workspace
+ * (>= pico_grad_sqnorm_workspace_bytes(n_chunks)), a second adds them in index order in double and stores
+ * *sumsq (device double). No atomics: the same tables and data give the same bits on every run. n_chunks = 0
+ * stores 0. The caller may all-reduce *sumsq over its model-parallel groups before pico_grad_clip_coef. */
+int64_t pico_grad_sqnorm_workspace_bytes(int64_t n_chunks);
+int pico_grad_sqnorm(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
+                     void* workspace, double* sumsq, void* stream);
+/* norm_coef (device float[2]): [0] = (float)sqrt(*sumsq), the total norm; [1] = fminf(1, (float)max_norm /
+ * ([0] + 1e-6f)), torch's clip coefficient. max_norm >= 0 (NaN is rejected). */
+int pico_grad_clip_coef(const double* sumsq, double max_norm, float* norm_coef, void* stream);
+/* The standalone clip, in place: bf16 g = bf16(float(g) * coef); fp32 main_grad g32 = float(bf16(float(bf16(g32))
+ * * coef)), the value the bf16 form would hold, so a later deferred-cast step rounds it to the same bits. Nothing
+ * is written when coef == 1 (the stored bf16 values would not change) or when the norm is not finite. */
+int pico_grad_scale(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
+                    const float* norm_coef, void* stream);
+/* pico_adamw_bf16 with g replaced by bf16(g * norm_coef[1]) in register: bit-identical to pico_grad_scale followed
+ * by pico_adamw_bf16 without the gradient write and re-read, and to pico_adamw_bf16 itself when the coefficient
+ * is 1. If norm_coef[0] is not finite (an inf / NaN gradient) the kernel writes nothing: parameters and both
+ * moments stay as they were. The host never reads the norm, so the caller's step counter still advances. */
+int pico_adamw_bf16_clip(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
+                         double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                         const float* norm_coef, void* stream);
 
 /* ---- softmax cross-entropy (mean over non-ignored rows) ----
  * logits: [rows, vocab] bf16, row stride ld (elements); target: [rows] int64.

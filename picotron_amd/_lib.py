@@ -18,6 +18,7 @@ K_SWIGLU_FWD, K_SWIGLU_BWD, K_ATTN_FWD, K_ATTN_BWD_PRE = 5, 6, 7, 8
 K_ATTN_BWD, K_ATTN_BWD_DQ, K_GRAD_ACCUM, K_CAST, K_SCALE, K_ATTN_MERGE = 9, 10, 11, 12, 13, 14
 K_EMBEDDING_BWD, K_CE_FWD, K_CE_BWD, K_TRANSPOSE, K_ATTN_BWD_DKV, K_SORT_IDS, K_ADAMW = 15, 16, 17, 18, 19, 20, 21
 K_ATTN_BWD_KV, K_ATTN_BWD_Q = 22, 23
+K_GRAD_SQNORM, K_GRAD_SCALE = 24, 25
 KERNEL_NAMES = {
     K_RMSNORM_FWD: "rmsnorm_fwd", K_RMSNORM_BWD: "rmsnorm_bwd", K_RMSNORM_DW: "rmsnorm_dw", K_ROPE: "rope",
     K_SWIGLU_FWD: "swiglu_fwd", K_SWIGLU_BWD: "swiglu_bwd", K_ATTN_FWD: "attn_fwd",
@@ -26,6 +27,7 @@ KERNEL_NAMES = {
     K_EMBEDDING_BWD: "embedding_bwd", K_CE_FWD: "cross_entropy_fwd", K_CE_BWD: "cross_entropy_bwd",
     K_TRANSPOSE: "transpose_bf16", K_ATTN_BWD_DKV: "attn_bwd_dkv", K_SORT_IDS: "sort_ids", K_ADAMW: "adamw",
     K_ATTN_BWD_KV: "attn_bwd_kv", K_ATTN_BWD_Q: "attn_bwd_q",
+    K_GRAD_SQNORM: "grad_sqnorm", K_GRAD_SCALE: "grad_scale",
 }
 
 # kernel-selection knobs (pico_select; PICO_SEL_* in include/picotron_hip.h)
@@ -93,6 +95,12 @@ _SIGNATURES = {
     "pico_adamw_chunk_elems": (c_i64, []),
     "pico_adamw_bf16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, c_i64, c_vp]),
+    "pico_adamw_bf16_clip": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_vp, c_vp]),
+    "pico_grad_sqnorm_workspace_bytes": (c_i64, [c_i64]),
+    "pico_grad_sqnorm": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pico_grad_clip_coef": (ctypes.c_int, [c_vp, ctypes.c_double, c_vp, c_vp]),
+    "pico_grad_scale": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "pico_cross_entropy_fwd": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "pico_cross_entropy_fwd_grad": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "pico_ce_count": (ctypes.c_int, [c_vp, c_i64, c_i64, ctypes.c_float, c_vp, c_vp]),

@@ -10,11 +10,11 @@
 //   p -= lr * wd * p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;
 //   p -= (float)(lr / bc1) * m / (float)(sqrt(v) / sqrt(bc2) + eps),  bc_i = 1 - b_i^step (host, double).
 // Bytes per element: 8 read (p, g, m, v) + 6 written (p, m, v) for bf16 (10 read with an fp32 main_grad).
-#include "common.h"
+#include "optim_common.h"
 
 namespace {
 
-constexpr int CHUNK = 65536;  // elements per workgroup
+constexpr int CHUNK = OPT_CHUNK;  // elements per workgroup
 
 struct AdamHyper {
   double lr_wd, b1, b2, eps, bc2_sqrt;
@@ -29,31 +29,13 @@ PICO_DEV void adam_elem(float& p, float g, float& m, float& v, const AdamHyper& 
   p -= h.step_size * m / denom;
 }
 
-// tensors: [n_tensors][5] = (param, grad, exp_avg, exp_avg_sq pointers, grad_is_f32) as int64; sizes:
-// [n_tensors] numel; chunks: [n_chunks][2] (tensor index, first element).
-// grad_is_f32 = 1: the gradient is DataParallelBucket's averaged fp32 main_grad (its bf16 .grad cast
-// deferred, ref picotron/data_parallel/data_parallel.py:165): each element is rounded to bf16 in register
-// exactly as pico_cast_f32_bf16 would store it, so the step is bit-identical to cast-then-step, without the
-// bf16 .grad write and re-read.
-template <bool GF32>
-PICO_DEV void load_grad8(const void* g, int64_t i, float (&out)[8]) {
-  if constexpr (GF32) {
-    const f32x4 a = reinterpret_cast<const f32x4*>((const float*)g + i)[0];
-    const f32x4 b = reinterpret_cast<const f32x4*>((const float*)g + i)[1];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      out[j] = bf2f(f2bf(a[j]));
-      out[4 + j] = bf2f(f2bf(b[j]));
-    }
-  } else {
-    const u16x8 gv = *reinterpret_cast<const u16x8*>((const bf16_t*)g + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] = bf2f(gv[j]);
-  }
-}
-
-template <bool GF32>
-PICO_DEV void adamw_chunk(bf16_t* p, const void* g, bf16_t* m, bf16_t* v, int64_t n, int64_t c0, const AdamHyper& h) {
+// The device tables and load_grad8 (the fp32 main_grad form, grad_is_f32 = 1) are in optim_common.h.
+// CLIP: the gradient is first scaled by the clip coefficient and rounded to bf16, g = bf16(g * coef): the value
+// pico_grad_scale would have stored, so the step is bit-identical to scale-then-step without the gradient
+// write and re-read (coef = 1: g unchanged, bit-identical to the plain step).
+template <bool GF32, bool CLIP>
+PICO_DEV void adamw_chunk(bf16_t* p, const void* g, bf16_t* m, bf16_t* v, int64_t n, int64_t c0, const AdamHyper& h,
+                          float coef) {
   const int64_t end = min(n, c0 + CHUNK);
   const bool vec = ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0) &&
                    (((uintptr_t)g & (GF32 ? 31 : 15)) == 0) && (n % 8 == 0);
@@ -66,6 +48,7 @@ PICO_DEV void adamw_chunk(bf16_t* p, const void* g, bf16_t* m, bf16_t* v, int64_
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float pf = bf2f(pv[j]), mf = bf2f(mv[j]), vf = bf2f(vv[j]);
+        if constexpr (CLIP) gf[j] = bf2f(f2bf(gf[j] * coef));
         adam_elem(pf, gf[j], mf, vf, h);
         pv[j] = f2bf(pf);
         mv[j] = f2bf(mf);
@@ -78,7 +61,8 @@ PICO_DEV void adamw_chunk(bf16_t* p, const void* g, bf16_t* m, bf16_t* v, int64_
   } else {
     for (int64_t i = c0 + threadIdx.x; i < end; i += 256) {
       float pf = bf2f(p[i]), mf = bf2f(m[i]), vf = bf2f(v[i]);
-      const float gf = GF32 ? bf2f(f2bf(((const float*)g)[i])) : bf2f(((const bf16_t*)g)[i]);
+      float gf = load_grad1<GF32>(g, i);
+      if constexpr (CLIP) gf = bf2f(f2bf(gf * coef));
       adam_elem(pf, gf, mf, vf, h);
       p[i] = f2bf(pf);
       m[i] = f2bf(mf);
@@ -87,17 +71,34 @@ PICO_DEV void adamw_chunk(bf16_t* p, const void* g, bf16_t* m, bf16_t* v, int64_
   }
 }
 
-__global__ __launch_bounds__(256) void adamw_bf16_kernel(const int64_t* __restrict__ tensors,
-                                                         const int64_t* __restrict__ sizes,
-                                                         const int64_t* __restrict__ chunks, AdamHyper h) {
+template <bool CLIP>
+PICO_DEV void adamw_block(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, const AdamHyper& h,
+                          float coef) {
   const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
   const int64_t* t = tensors + 5 * ti;
   bf16_t* p = (bf16_t*)t[0];
   const void* g = (const void*)t[1];
   bf16_t* m = (bf16_t*)t[2];
   bf16_t* v = (bf16_t*)t[3];
-  if (t[4]) adamw_chunk<true>(p, g, m, v, sizes[ti], c0, h);
-  else adamw_chunk<false>(p, g, m, v, sizes[ti], c0, h);
+  if (t[4]) adamw_chunk<true, CLIP>(p, g, m, v, sizes[ti], c0, h, coef);
+  else adamw_chunk<false, CLIP>(p, g, m, v, sizes[ti], c0, h, coef);
+}
+
+__global__ __launch_bounds__(256) void adamw_bf16_kernel(const int64_t* __restrict__ tensors,
+                                                         const int64_t* __restrict__ sizes,
+                                                         const int64_t* __restrict__ chunks, AdamHyper h) {
+  adamw_block<false>(tensors, sizes, chunks, h, 1.0f);
+}
+
+// norm_coef: device (gradient norm, clip coefficient), as pico_grad_clip_coef leaves them. A non-finite norm
+// (an inf / NaN gradient somewhere in the list) skips the update: nothing is written.
+__global__ __launch_bounds__(256) void adamw_bf16_clip_kernel(const int64_t* __restrict__ tensors,
+                                                              const int64_t* __restrict__ sizes,
+                                                              const int64_t* __restrict__ chunks, AdamHyper h,
+                                                              const float* __restrict__ norm_coef) {
+  const float norm = norm_coef[0], coef = norm_coef[1];
+  if (!isfinite(norm)) return;
+  adamw_block<true>(tensors, sizes, chunks, h, coef);
 }
 
 }  // namespace
@@ -125,5 +126,32 @@ extern "C" int pico_adamw_bf16(const int64_t* tensors, const int64_t* sizes, con
   h.step_size = (float)((double)lr / bc1);
   hipStream_t s = (hipStream_t)stream;
   PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw", adamw_bf16_kernel, dim3((int)n_chunks), dim3(256), 0, s, tensors, sizes, chunks, h));
+  return 0;
+}
+
+// pico_adamw_bf16 with the gradient clip folded in: the same checks and host-side hyper-parameters, plus the
+// device (norm, coefficient) pair. Timed under PICO_K_ADAMW.
+extern "C" int pico_adamw_bf16_clip(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks,
+                                    int64_t n_chunks, double lr, double beta1, double beta2, double eps,
+                                    double weight_decay, int64_t step, const float* norm_coef, void* stream) {
+  PICO_REQUIRE(n_chunks >= 0 && n_chunks < (1ll << 31), "pico_adamw_bf16_clip: bad chunk count");
+  PICO_REQUIRE(step >= 1, "pico_adamw_bf16_clip: step must be >= 1");
+  PICO_REQUIRE(lr >= 0.0 && eps >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+               "pico_adamw_bf16_clip: invalid hyper-parameters");
+  PICO_REQUIRE(norm_coef, "pico_adamw_bf16_clip: null norm_coef");
+  if (n_chunks == 0) return 0;
+  PICO_REQUIRE(tensors && sizes && chunks, "pico_adamw_bf16_clip: null table");
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  AdamHyper h;
+  h.lr_wd = (double)lr * (double)weight_decay;
+  h.b1 = beta1;
+  h.b2 = beta2;
+  h.eps = eps;
+  h.bc2_sqrt = sqrt(bc2);
+  h.step_size = (float)((double)lr / bc1);
+  hipStream_t s = (hipStream_t)stream;
+  PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_clip", adamw_bf16_clip_kernel, dim3((int)n_chunks), dim3(256), 0, s, tensors,
+                       sizes, chunks, h, norm_coef));
   return 0;
 }

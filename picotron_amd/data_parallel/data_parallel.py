@@ -76,8 +76,10 @@ class DataParallelBucket(nn.Module):
         bucket's bf16 view WITHOUT the fp32 -> bf16 cast of ref :165 having run; picotron_amd.optim.AdamW reads
         the averaged fp32 main_grad instead and rounds it to bf16 in register exactly as the cast would
         (bit-identical step, no bf16 .grad write + re-read: 4 B per parameter per step). Any other optimizer gets
-        the cast run for it by a step pre-hook before it steps; code that reads `.grad` outside an optimizer step
-        (clip_grad_norm_, grad-norm logging, checkpointing grads) must call materialize_grads() first."""
+        the cast run for it by a step pre-hook before it steps. picotron_amd.optim.clip_grad_norm_ / get_grad_norm
+        (and AdamW(max_grad_norm=...)) read the fp32 main_grad the same way and need no materialize_grads(); any
+        other code that reads `.grad` outside an optimizer step (torch.nn.utils.clip_grad_norm_, checkpointing
+        grads) must call materialize_grads() first."""
         super().__init__()
         self.module = module
         self.require_backward_grad_sync = True

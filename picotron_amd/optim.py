@@ -7,7 +7,15 @@ parameter dtype), so checkpoints and LR schedules see a torch AdamW. The update 
 AdamW expression order and types (decoupled weight decay; see csrc/adamw.hip). Parameters and
 gradients must be bf16 HIP tensors (the training dtype of the hot path); anything else raises —
 there is no CPU or eager fallback.
+
+Global-norm gradient clipping (csrc/grad_clip.hip) on the same device tables: `clip_grad_norm_` /
+`get_grad_norm` replace `torch.nn.utils.clip_grad_norm_` / `get_total_norm` (one launch over the whole list, the
+norm and the coefficient stay on the device, fixed summation order, fp32 main_grads of
+DataParallelBucket(defer_grad_cast=True) read in place, one norm under tensor / pipeline parallelism), and
+`AdamW(max_grad_norm=...)` folds the clip into the optimizer's gradient load.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -24,20 +32,210 @@ def _deferred_grad(p):
     return g32
 
 
+def _new_tables(numels, dev):
+    """Device tables of one parameter set: sizes / 64 Ki-element chunks (fixed for the set) and the [n][5] pointer
+    table with its two pinned staging buffers (see _sync_ptrs)."""
+    chunk = int(_lib.load().pico_adamw_chunk_elems())
+    sizes = torch.tensor(numels, dtype=torch.int64)
+    chunks = torch.tensor([(i, c) for i, n in enumerate(numels) for c in range(0, n, chunk)],
+                          dtype=torch.int64).reshape(-1, 2)
+    return {"tens": torch.empty((len(numels), 5), dtype=torch.int64, device=dev), "sizes": sizes.to(dev),
+            "chunks": chunks.to(dev), "chunks_host": chunks, "n_chunks": chunks.shape[0], "ptrs": None, "turn": 0,
+            "host": [torch.empty((len(numels), 5), dtype=torch.int64).pin_memory() for _ in range(2)],
+            "done": [None, None], "norm": None}
+
+
+def _sync_ptrs(ent, ptrs, dev):
+    """Re-upload the pointer table only when a pointer changed (persistent gradients: never after the first
+    step); two pinned staging buffers used in turn."""
+    if ptrs != ent["ptrs"]:
+        i = ent["turn"]
+        if ent["done"][i] is not None:  # this staging buffer may still be feeding its previous copy
+            ent["done"][i].synchronize()
+        ent["host"][i].numpy()[:] = ptrs
+        ent["tens"].copy_(ent["host"][i], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        ent["done"][i] = ev
+        ent["turn"] = 1 - i
+        ent["ptrs"] = ptrs
+
+
+def select_norm_params(params, tp_rank, tp_world_size):
+    """Which of `params` this rank adds to its local sum of squares, one bool each, so that the sum over a
+    tensor-parallel group counts every element of the model once: a parameter tagged `_pico_tp_sharded` (a
+    ColumnParallelLinear / RowParallelLinear / VocabParallelEmbedding shard) is this rank's alone and always
+    counts; an untagged one (RMSNorm weights, the row-parallel bias) is replicated on every tp rank and counts
+    on tp rank 0 only. tp_world_size 1: everything counts."""
+    if tp_world_size <= 1 or tp_rank == 0:
+        return [True] * len(params)
+    return [bool(getattr(p, "_pico_tp_sharded", False)) for p in params]
+
+
+def _norm_groups(groups):
+    """(process groups the sum of squares is all-reduced over, tp_rank, tp_world_size for select_norm_params).
+    groups None: tp_group if tp > 1 and pp_group if pp > 1 of the process_group_manager, when it is set up (DP and
+    CP ranks hold identical synced gradients: nothing to reduce); groups=(): local only, every parameter counts."""
+    from . import process_group_manager as pgm
+    m = pgm.process_group_manager
+    if groups is None:
+        groups = []
+        if m is not None:
+            if m.tp_world_size > 1:
+                groups.append(m.tp_group)
+            if m.pp_world_size > 1:
+                groups.append(m.pp_group)
+    groups = tuple(groups)
+    if not groups or m is None:
+        return groups, 0, 1
+    return groups, m.tp_rank, m.tp_world_size
+
+
+def _sqnorm(lib, ent, keep, stream):
+    """Launch pico_grad_sqnorm over the chunks of the kept tensors of a table set; returns its 1-element device
+    double. The chunk list, the partial-sum workspace and the result live next to the tables (allocated once)."""
+    keep = tuple(keep)
+    nrm = ent["norm"]
+    if nrm is None or nrm["keep"] != keep:
+        dev = ent["tens"].device
+        if all(keep):
+            chunks, n = ent["chunks"], ent["n_chunks"]
+        else:
+            host = ent["chunks_host"]
+            host = host[torch.tensor(keep, dtype=torch.bool)[host[:, 0]]] if host.shape[0] else host
+            chunks, n = host.to(dev), host.shape[0]
+        ws = int(lib.pico_grad_sqnorm_workspace_bytes(n))
+        nrm = ent["norm"] = {"keep": keep, "chunks": chunks, "n_chunks": n,
+                             "ws": torch.empty(max(ws // 4, 1), dtype=torch.float32, device=dev),
+                             "sumsq": torch.empty(1, dtype=torch.float64, device=dev)}
+    _lib.check(lib.pico_grad_sqnorm(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(nrm["chunks"]),
+                                    nrm["n_chunks"], _lib.ptr(nrm["ws"]), _lib.ptr(nrm["sumsq"]), stream),
+               "pico_grad_sqnorm")
+    return nrm["sumsq"]
+
+
+def _norm_coef(lib, sums, groups, max_norm, stream):
+    """The device (total norm, clip coefficient) pair from the table sets' sums of squares: added in list order,
+    all-reduced (SUM, double) over each group, then pico_grad_clip_coef. Nothing is read on the host."""
+    total = sums[0]
+    for s in sums[1:]:
+        total = total + s
+    if groups:
+        import torch.distributed as dist
+        for g in groups:
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=g)
+    out = torch.empty(2, dtype=torch.float32, device=total.device)
+    _lib.check(lib.pico_grad_clip_coef(_lib.ptr(total), float(max_norm), _lib.ptr(out), stream), "pico_grad_clip_coef")
+    return out
+
+
+_STANDALONE = {}  # clip_grad_norm_ / get_grad_norm: tables per parameter list, as AdamW._tables
+
+
+def _grad_tables(parameters):
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = [p for p in parameters if p.grad is not None]
+    if not params:
+        return params, None
+    ptrs = []
+    for p in params:
+        g32 = _deferred_grad(p)
+        g = g32 if g32 is not None else p.grad
+        if not g.is_cuda or (g32 is None and g.dtype != torch.bfloat16):
+            raise TypeError(f"picotron_amd.optim: gradients must be bf16 HIP tensors, got {g.dtype} on {g.device}")
+        if g.is_sparse or not g.is_contiguous():
+            raise ValueError("picotron_amd.optim: dense contiguous gradients only")
+        ptrs.append((0, g.data_ptr(), 0, 0, 0 if g32 is None else 1))
+    dev = params[0].grad.device
+    key = (dev, tuple((p.data_ptr(), p.numel()) for p in params))
+    ent = _STANDALONE.get(key)
+    if ent is None:
+        ent = _new_tables([p.numel() for p in params], dev)
+        if len(_STANDALONE) > 16:
+            _STANDALONE.clear()
+        _STANDALONE[key] = ent
+    _sync_ptrs(ent, ptrs, dev)
+    return params, ent
+
+
+def _total_norm(parameters, max_norm, groups):
+    params, ent = _grad_tables(parameters)
+    if ent is None:
+        return None, None, None
+    lib = _lib.load()
+    stream = _lib.stream_of(params[0].grad)
+    groups, tp_rank, tp_world = _norm_groups(groups)
+    s = _sqnorm(lib, ent, select_norm_params(params, tp_rank, tp_world), stream)
+    return _norm_coef(lib, [s], groups, max_norm, stream), ent, stream
+
+
+@torch.no_grad()
+def get_grad_norm(parameters, *, groups=None):
+    """The global L2 norm of the gradients of `parameters`, a 0-dim fp32 device tensor (no host read). bf16
+    gradients, or the fp32 main_grad DataParallelBucket(defer_grad_cast=True) left (read as bf16(g), the value the
+    deferred cast would store: no materialize_grads() needed). `groups`: see clip_grad_norm_."""
+    nc, _, _ = _total_norm(parameters, math.inf, groups)
+    return torch.zeros((), dtype=torch.float32) if nc is None else nc[0]
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None, *, groups=None):
+    """torch.nn.utils.clip_grad_norm_ on the gfx950 kernels: scales the gradients in place by
+    min(1, max_norm / (total_norm + 1e-6)) and returns the total pre-clip norm (0-dim fp32 device tensor). Three
+    launches over the whole list; the norm and the coefficient stay on the device, so the host does not wait
+    (error_if_nonfinite=True is the one path that reads the norm: RuntimeError, as torch). A non-finite norm
+    leaves the gradients as they are. A deferred fp32 main_grad is read and scaled in place (to the value its
+    bf16 form would hold), without materialize_grads().
+
+    Model parallelism: one norm for the whole model. Each tensor-parallel rank sums its own shards (parameters
+    tagged `_pico_tp_sharded` by tensor_parallel.py) and tp rank 0 the replicated parameters, then the sum of
+    squares is all-reduced over every process group in `groups` (None: the process_group_manager's tp and pp
+    groups where > 1; (): none — the local norm of everything this rank holds)."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError("picotron_amd.optim.clip_grad_norm_: norm_type 2 only")
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm must be >= 0, got {max_norm}")
+    nc, ent, stream = _total_norm(parameters, max_norm, groups)
+    if nc is None:
+        return torch.zeros((), dtype=torch.float32)
+    if error_if_nonfinite and not bool(torch.isfinite(nc[0])):
+        raise RuntimeError("The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot "
+                           "be clipped. To disable this error and scale the gradients by the non-finite norm "
+                           "anyway, set `error_if_nonfinite=False`")
+    _lib.check(_lib.load().pico_grad_scale(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
+                                           ent["n_chunks"], _lib.ptr(nc), stream), "pico_grad_scale")
+    return nc[0]
+
+
 class AdamW(torch.optim.Optimizer):
     # reads DataParallelBucket(defer_grad_cast=True)'s fp32 main_grad itself: the bucket's step pre-hook leaves
     # the deferred cast to this optimizer (see data_parallel.py)
     reads_deferred_grads = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
-                 maximize=False, foreach=None, capturable=False, differentiable=False, fused=None):
+                 maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                 max_grad_norm=None, grad_norm_groups=None):
+        """max_grad_norm (an extension; None: off, the step runs exactly as without it): clip the global L2
+        gradient norm inside the step. One norm over every parameter that has a gradient (all param groups and
+        step counts; `grad_norm_groups`: the `groups` of clip_grad_norm_), then pico_adamw_bf16_clip scales each
+        gradient as it loads it — bit-identical to clip_grad_norm_ followed by the plain step, without the
+        gradient write and re-read. `self.grad_norm` is the pre-clip norm (0-dim device tensor) after each step.
+        The host never reads the norm: when it is not finite the kernel writes nothing (parameters and moments
+        stay as they were) but the per-parameter `step` counters have already advanced; watch `grad_norm`."""
         if amsgrad or maximize or capturable or differentiable:
             raise NotImplementedError("picotron_amd.optim.AdamW: amsgrad / maximize / capturable / differentiable")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"invalid AdamW hyper-parameters lr={lr} betas={betas} eps={eps}")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:  # negative or NaN
+            raise ValueError(f"invalid AdamW max_grad_norm={max_grad_norm}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                         foreach=None, capturable=False, differentiable=False, fused=fused)
         super().__init__(params, defaults)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm_groups = grad_norm_groups
+        self.grad_norm = None
         # per (group, parameter set): device tables of sizes / 64 Ki-element chunks (fixed for the set) and of
         # the (param, grad, exp_avg, exp_avg_sq) pointers, re-uploaded only when a pointer changed (persistent
         # gradients: never after the first step); two pinned staging buffers used in turn
@@ -49,15 +247,7 @@ class AdamW(torch.optim.Optimizer):
         key = (gi, tuple((p.data_ptr(), p.numel()) for p in params))
         ent = self._tables.get(key)
         if ent is None:
-            chunk = int(_lib.load().pico_adamw_chunk_elems())
-            dev = params[0].device
-            sizes = torch.tensor([p.numel() for p in params], dtype=torch.int64)
-            chunks = torch.tensor([(i, c) for i, p in enumerate(params) for c in range(0, p.numel(), chunk)],
-                                  dtype=torch.int64).reshape(-1, 2)
-            ent = {"tens": torch.empty((len(params), 5), dtype=torch.int64, device=dev), "sizes": sizes.to(dev),
-                   "chunks": chunks.to(dev), "n_chunks": chunks.shape[0], "ptrs": None, "turn": 0,
-                   "host": [torch.empty((len(params), 5), dtype=torch.int64).pin_memory() for _ in range(2)],
-                   "done": [None, None]}
+            ent = _new_tables([p.numel() for p in params], params[0].device)
             if len(self._tables) > 64:  # parameter sets keep changing (step counts diverging): keep the map small
                 self._tables.clear()
             self._tables[key] = ent
@@ -67,17 +257,7 @@ class AdamW(torch.optim.Optimizer):
             ptrs.append((p.data_ptr(), (g32 if g32 is not None else p.grad).data_ptr(),
                          self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
                          0 if g32 is None else 1))
-        if ptrs != ent["ptrs"]:
-            i = ent["turn"]
-            if ent["done"][i] is not None:  # this staging buffer may still be feeding its previous copy
-                ent["done"][i].synchronize()
-            ent["host"][i].numpy()[:] = ptrs
-            ent["tens"].copy_(ent["host"][i], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(params[0].device))
-            ent["done"][i] = ev
-            ent["turn"] = 1 - i
-            ent["ptrs"] = ptrs
+        _sync_ptrs(ent, ptrs, params[0].device)
         return ent
 
     def zero_grad(self, set_to_none=True):
@@ -97,6 +277,36 @@ class AdamW(torch.optim.Optimizer):
         if grads:
             torch._foreach_zero_(grads)
 
+    def _advance(self, group):
+        """Validate a group's parameters that have a gradient, create / advance their states, and return
+        [(step count, parameters)] sorted by step count (empty: no gradient in the group)."""
+        params = [p for p in group["params"] if p.grad is not None]
+        if not params:
+            return []
+        # validate everything before touching any state (a failed step leaves the state as it was)
+        for p in params:
+            if not (p.is_cuda and p.dtype == torch.bfloat16 and p.grad.dtype == torch.bfloat16):
+                raise TypeError("picotron_amd.optim.AdamW: parameters and gradients must be bf16 HIP tensors, "
+                                f"got {p.dtype} / {p.grad.dtype} on {p.device}")
+            if p.grad.is_sparse or not p.grad.is_contiguous() or not p.is_contiguous():
+                raise ValueError("picotron_amd.optim.AdamW: dense contiguous parameters and gradients only")
+        # per-parameter step counts, as torch.optim.AdamW keeps them: a parameter that had no gradient on
+        # some steps (frozen for a while, an idle pipeline stage) advances only when it has one; one
+        # launch per distinct step count. `step` stays a CPU scalar (a loaded state may carry it on the
+        # device: moved back once, so reading it costs no host sync per step).
+        by_step = {}
+        for p in params:
+            st = self.state[p]
+            if not st:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            elif st["step"].device.type != "cpu":
+                st["step"] = st["step"].detach().to("cpu", torch.float32)
+            st["step"] += 1
+            by_step.setdefault(int(st["step"].item()), []).append(p)
+        return sorted(by_step.items())
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -104,37 +314,36 @@ class AdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        if self.max_grad_norm is not None:
+            self._step_clipped(lib)
+            return loss
         for gi, group in enumerate(self.param_groups):
-            params = [p for p in group["params"] if p.grad is not None]
-            if not params:
-                continue
-            # validate everything before touching any state (a failed step leaves the state as it was)
-            for p in params:
-                if not (p.is_cuda and p.dtype == torch.bfloat16 and p.grad.dtype == torch.bfloat16):
-                    raise TypeError("picotron_amd.optim.AdamW: parameters and gradients must be bf16 HIP tensors, "
-                                    f"got {p.dtype} / {p.grad.dtype} on {p.device}")
-                if p.grad.is_sparse or not p.grad.is_contiguous() or not p.is_contiguous():
-                    raise ValueError("picotron_amd.optim.AdamW: dense contiguous parameters and gradients only")
-            # per-parameter step counts, as torch.optim.AdamW keeps them: a parameter that had no gradient on
-            # some steps (frozen for a while, an idle pipeline stage) advances only when it has one; one
-            # launch per distinct step count. `step` stays a CPU scalar (a loaded state may carry it on the
-            # device: moved back once, so reading it costs no host sync per step).
-            by_step = {}
-            for p in params:
-                st = self.state[p]
-                if not st:
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                elif st["step"].device.type != "cpu":
-                    st["step"] = st["step"].detach().to("cpu", torch.float32)
-                st["step"] += 1
-                by_step.setdefault(int(st["step"].item()), []).append(p)
             beta1, beta2 = group["betas"]
-            for step, ps in sorted(by_step.items()):
+            for step, ps in self._advance(group):
                 ent = self._group_tables(gi, ps)
                 _lib.check(lib.pico_adamw_bf16(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
                                                ent["n_chunks"], float(group["lr"]), float(beta1), float(beta2),
                                                float(group["eps"]), float(group["weight_decay"]), step,
                                                _lib.stream_of(ps[0])), "pico_adamw_bf16")
         return loss
+
+    def _step_clipped(self, lib):
+        """The step with max_grad_norm: every (group, step count) table set first, one global norm over all of
+        them, then one pico_adamw_bf16_clip launch per set with the same device (norm, coefficient) pair."""
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            for step, ps in self._advance(group):
+                work.append((group, step, ps, self._group_tables(gi, ps)))
+        if not work:
+            return
+        stream = _lib.stream_of(work[0][2][0])
+        groups, tp_rank, tp_world = _norm_groups(self.grad_norm_groups)
+        sums = [_sqnorm(lib, ent, select_norm_params(ps, tp_rank, tp_world), stream) for _, _, ps, ent in work]
+        nc = _norm_coef(lib, sums, groups, self.max_grad_norm, stream)
+        for group, step, ps, ent in work:
+            beta1, beta2 = group["betas"]
+            _lib.check(lib.pico_adamw_bf16_clip(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
+                                                ent["n_chunks"], float(group["lr"]), float(beta1), float(beta2),
+                                                float(group["eps"]), float(group["weight_decay"]), step,
+                                                _lib.ptr(nc), stream), "pico_adamw_bf16_clip")
+        self.grad_norm = nc[0]

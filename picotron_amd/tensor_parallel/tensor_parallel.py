@@ -11,6 +11,8 @@ MI355X-native differences (same numbers):
     ONE f region (all-reduce of the input gradient) around the fused q|k|v + RoPE + attention (gate|up +
     SwiGLU) op on the local shards, instead of one per projection — one collective instead of three
     (two) per layer backward, the same sum;
+  * every sharded parameter carries `_pico_tp_sharded = True`, so picotron_amd.optim's global gradient norm
+    counts the shards on every rank and the replicated parameters (RMSNorm weights, the row-parallel bias) once;
   * apply_tensor_parallel(model, shard_weights=True) converts an already initialised model in place
     (each new layer takes its rank's shard of the existing weight) — the reference re-initialises.
 """
@@ -90,8 +92,10 @@ class ColumnParallelLinear(nn.Module):
         self.gather_output = gather_output
         self.async_all_reduce = async_all_reduce
         self.weight = nn.Parameter(torch.empty(self.output_size_per_partition, self.in_features))
+        self.weight._pico_tp_sharded = True  # this rank's rows only: counted on every rank in the global grad norm
         if bias:
             self.bias = nn.Parameter(torch.zeros(self.output_size_per_partition))
+            self.bias._pico_tp_sharded = True
         else:
             self.register_parameter("bias", None)
         self.reset_parameters()
@@ -127,8 +131,9 @@ class RowParallelLinear(nn.Module):
         assert in_features % self.tp_world_size == 0, "Hidden dimension must be divisible by the tensor parallel world size"
         self.input_size_per_partition = in_features // self.tp_world_size
         self.weight = nn.Parameter(torch.empty(self.out_features, self.input_size_per_partition))
+        self.weight._pico_tp_sharded = True
         if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_features))
+            self.bias = nn.Parameter(torch.zeros(self.out_features))  # replicated: no tag (counted on tp rank 0)
         else:
             self.register_parameter("bias", None)
         self.reset_parameters()
@@ -169,6 +174,7 @@ class VocabParallelEmbedding(nn.Module):
             num_embeddings, self.tp_rank, self.tp_world_size)
         self.num_embeddings_per_partition = self.vocab_end_index - self.vocab_start_index
         self.weight = nn.Parameter(torch.empty(self.num_embeddings_per_partition, self.embedding_dim))
+        self.weight._pico_tp_sharded = True
         self.reset_parameters()
 
     def _vocab_range_from_global_vocab_size(self, global_vocab_size: int, rank: int, world_size: int):
