@@ -28,6 +28,8 @@
  *                             <- torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm): no reference call
  *                                 (the reference trains unclipped); what a Llama pre-training recipe adds between
  *                                 the last backward and optimizer.step() (ref train.py:235)
+ *   pico_adamw_master         <- the same step on fp32 master weights and fp32 moments (mixed-precision recipes'
+ *                                 optimizer; no reference call: the reference's AdamW steps the bf16 tensors)
  *   pico_sort_ids             <- the stable id sort inside F.embedding's backward (ref picotron/model.py:223-224)
  *   pico_embedding_bwd        <- backward of F.embedding (ref picotron/model.py:223-224) + the micro-batch
  *                                 gradient accumulation (data_parallel.py:131 / autograd's grad += dW)
@@ -295,6 +297,20 @@ int pico_grad_scale(const int64_t* tensors, const int64_t* sizes, const int64_t*
 int pico_adamw_bf16_clip(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
                          double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                          const float* norm_coef, void* stream);
+
+/* ---- AdamW on fp32 master weights and fp32 moments under the bf16 model parameters, one launch ----
+ * The Megatron / DeepSpeed / torch-AMP arrangement (no reference call: the reference steps bf16 tensors). `tensors`
+ * keeps pico_adamw_bf16's [n_tensors][5] layout (pico_grad_sqnorm / pico_grad_scale work on it unchanged), but its
+ * exp_avg / exp_avg_sq columns point at FP32 buffers and its param column at the bf16 model parameter, which is
+ * written as bf16(master), round to nearest even, and never read. masters: device int64 [n_tensors], the fp32
+ * master parameter addresses. The gradient value is the bf16 kernels' (bf16 .grad, or bf16(main_grad) when
+ * grad_is_f32); the update is ATen's fused AdamW on fp32 tensors (double hyper-parameters, same expression order);
+ * master and both moments are stored as fp32. norm_coef NULL: no clip; else as pico_adamw_bf16_clip (g = bf16(g *
+ * norm_coef[1]); nothing is written when norm_coef[0] is not finite). 28 bytes per element (30 with an fp32
+ * main_grad). Timed under PICO_K_ADAMW. */
+int pico_adamw_master(const int64_t* tensors, const int64_t* masters, const int64_t* sizes, const int64_t* chunks,
+                      int64_t n_chunks, double lr, double beta1, double beta2, double eps, double weight_decay,
+                      int64_t step, const float* norm_coef, void* stream);
 
 /* ---- softmax cross-entropy (mean over non-ignored rows) ----
  * logits: [rows, vocab] bf16, row stride ld (elements); target: [rows] int64.

@@ -10,6 +10,7 @@
 //   p -= lr * wd * p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;
 //   p -= (float)(lr / bc1) * m / (float)(sqrt(v) / sqrt(bc2) + eps),  bc_i = 1 - b_i^step (host, double).
 // Bytes per element: 8 read (p, g, m, v) + 6 written (p, m, v) for bf16 (10 read with an fp32 main_grad).
+// pico_adamw_master (below) keeps an fp32 master copy of each parameter and fp32 moments: 28 bytes per element.
 #include "optim_common.h"
 
 namespace {
@@ -101,6 +102,94 @@ __global__ __launch_bounds__(256) void adamw_bf16_clip_kernel(const int64_t* __r
   adamw_block<true>(tensors, sizes, chunks, h, coef);
 }
 
+// ---- fp32 master weights and fp32 moments under the bf16 model parameter (pico_adamw_master) ----
+// The gradient value is the bf16 kernel's (load_grad8 / load_grad1, then the clip's bf16(g * coef)); adam_elem then
+// runs on the fp32 master p32 and the fp32 m, v, which are stored as fp32: ATen's fused AdamW on fp32 tensors. The
+// bf16 model parameter is bf16(p32), written and never read. Bytes per element: 14 read (p32, g, m, v) + 14 written
+// (p32, m, v, p), 16 read with an fp32 main_grad. Vector path: 8 elements per lane, two 16-byte accesses per fp32
+// operand and one per bf16 operand (fp32 pointers 32-byte aligned, the rule of grad_vec_ok<true>).
+template <bool GF32, bool CLIP>
+PICO_DEV void adamw_master_chunk(bf16_t* p, float* p32, const void* g, float* m, float* v, int64_t n, int64_t c0,
+                                 const AdamHyper& h, float coef) {
+  const int64_t end = min(n, c0 + CHUNK);
+  const bool vec = (((uintptr_t)p & 15) == 0) && ((((uintptr_t)p32 | (uintptr_t)m | (uintptr_t)v) & 31) == 0) &&
+                   grad_vec_ok<GF32>(g, n);
+  if (vec) {
+    for (int64_t i = c0 + 8 * (int64_t)threadIdx.x; i < end; i += 8 * 256) {
+      f32x4 pw[2], mw[2], vw[2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        pw[k] = reinterpret_cast<const f32x4*>(p32 + i)[k];
+        mw[k] = reinterpret_cast<const f32x4*>(m + i)[k];
+        vw[k] = reinterpret_cast<const f32x4*>(v + i)[k];
+      }
+      float gf[8];
+      load_grad8<GF32>(g, i, gf);
+      u16x8 pv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float pf = pw[j / 4][j % 4], mf = mw[j / 4][j % 4], vf = vw[j / 4][j % 4];
+        if constexpr (CLIP) gf[j] = bf2f(f2bf(gf[j] * coef));
+        adam_elem(pf, gf[j], mf, vf, h);
+        pw[j / 4][j % 4] = pf;
+        mw[j / 4][j % 4] = mf;
+        vw[j / 4][j % 4] = vf;
+        pv[j] = f2bf(pf);
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        reinterpret_cast<f32x4*>(p32 + i)[k] = pw[k];
+        reinterpret_cast<f32x4*>(m + i)[k] = mw[k];
+        reinterpret_cast<f32x4*>(v + i)[k] = vw[k];
+      }
+      *reinterpret_cast<u16x8*>(p + i) = pv;
+    }
+  } else {
+    for (int64_t i = c0 + threadIdx.x; i < end; i += 256) {
+      float pf = p32[i], mf = m[i], vf = v[i];
+      float gf = load_grad1<GF32>(g, i);
+      if constexpr (CLIP) gf = bf2f(f2bf(gf * coef));
+      adam_elem(pf, gf, mf, vf, h);
+      p32[i] = pf;
+      m[i] = mf;
+      v[i] = vf;
+      p[i] = f2bf(pf);
+    }
+  }
+}
+
+template <bool CLIP>
+PICO_DEV void adamw_master_block(const int64_t* tensors, const int64_t* masters, const int64_t* sizes,
+                                 const int64_t* chunks, const AdamHyper& h, float coef) {
+  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
+  const int64_t* t = tensors + 5 * ti;
+  bf16_t* p = (bf16_t*)t[0];
+  float* p32 = (float*)masters[ti];
+  const void* g = (const void*)t[1];
+  float* m = (float*)t[2];
+  float* v = (float*)t[3];
+  if (t[4]) adamw_master_chunk<true, CLIP>(p, p32, g, m, v, sizes[ti], c0, h, coef);
+  else adamw_master_chunk<false, CLIP>(p, p32, g, m, v, sizes[ti], c0, h, coef);
+}
+
+__global__ __launch_bounds__(256) void adamw_master_kernel(const int64_t* __restrict__ tensors,
+                                                           const int64_t* __restrict__ masters,
+                                                           const int64_t* __restrict__ sizes,
+                                                           const int64_t* __restrict__ chunks, AdamHyper h) {
+  adamw_master_block<false>(tensors, masters, sizes, chunks, h, 1.0f);
+}
+
+// norm_coef as in adamw_bf16_clip_kernel: a non-finite norm writes nothing (master, moments, parameter).
+__global__ __launch_bounds__(256) void adamw_master_clip_kernel(const int64_t* __restrict__ tensors,
+                                                                const int64_t* __restrict__ masters,
+                                                                const int64_t* __restrict__ sizes,
+                                                                const int64_t* __restrict__ chunks, AdamHyper h,
+                                                                const float* __restrict__ norm_coef) {
+  const float norm = norm_coef[0], coef = norm_coef[1];
+  if (!isfinite(norm)) return;
+  adamw_master_block<true>(tensors, masters, sizes, chunks, h, coef);
+}
+
 }  // namespace
 
 extern "C" int64_t pico_adamw_chunk_elems(void) { return CHUNK; }
@@ -153,5 +242,37 @@ extern "C" int pico_adamw_bf16_clip(const int64_t* tensors, const int64_t* sizes
   hipStream_t s = (hipStream_t)stream;
   PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_clip", adamw_bf16_clip_kernel, dim3((int)n_chunks), dim3(256), 0, s, tensors,
                        sizes, chunks, h, norm_coef));
+  return 0;
+}
+
+// The step on fp32 master weights and fp32 moments: pico_adamw_bf16_clip's checks and host-side hyper-parameters,
+// plus the masters table; norm_coef NULL: no clip. Timed under PICO_K_ADAMW.
+extern "C" int pico_adamw_master(const int64_t* tensors, const int64_t* masters, const int64_t* sizes,
+                                 const int64_t* chunks, int64_t n_chunks, double lr, double beta1, double beta2,
+                                 double eps, double weight_decay, int64_t step, const float* norm_coef, void* stream) {
+  PICO_REQUIRE(n_chunks >= 0 && n_chunks < (1ll << 31), "pico_adamw_master: bad chunk count");
+  PICO_REQUIRE(step >= 1, "pico_adamw_master: step must be >= 1");
+  PICO_REQUIRE(lr >= 0.0 && eps >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+               "pico_adamw_master: invalid hyper-parameters");
+  if (n_chunks == 0) return 0;
+  PICO_REQUIRE(tensors && sizes && chunks, "pico_adamw_master: null table");
+  PICO_REQUIRE(masters, "pico_adamw_master: null masters table");
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  AdamHyper h;
+  h.lr_wd = (double)lr * (double)weight_decay;
+  h.b1 = beta1;
+  h.b2 = beta2;
+  h.eps = eps;
+  h.bc2_sqrt = sqrt(bc2);
+  h.step_size = (float)((double)lr / bc1);
+  hipStream_t s = (hipStream_t)stream;
+  if (norm_coef) {
+    PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_master_clip", adamw_master_clip_kernel, dim3((int)n_chunks), dim3(256), 0,
+                         s, tensors, masters, sizes, chunks, h, norm_coef));
+  } else {
+    PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_master", adamw_master_kernel, dim3((int)n_chunks), dim3(256), 0, s,
+                         tensors, masters, sizes, chunks, h));
+  }
   return 0;
 }

@@ -13,6 +13,9 @@ Global-norm gradient clipping (csrc/grad_clip.hip) on the same device tables: `c
 norm and the coefficient stay on the device, fixed summation order, fp32 main_grads of
 DataParallelBucket(defer_grad_cast=True) read in place, one norm under tensor / pipeline parallelism), and
 `AdamW(max_grad_norm=...)` folds the clip into the optimizer's gradient load.
+
+`AdamW(master_weights=True)` (pico_adamw_master): fp32 master weights and fp32 moments under the bf16 parameters, the
+mixed-precision recipes' arrangement, on the same tables and in the same one launch.
 """
 import math
 
@@ -32,16 +35,20 @@ def _deferred_grad(p):
     return g32
 
 
-def _new_tables(numels, dev):
+def _new_tables(numels, dev, masters=False):
     """Device tables of one parameter set: sizes / 64 Ki-element chunks (fixed for the set) and the [n][5] pointer
-    table with its two pinned staging buffers (see _sync_ptrs)."""
+    table with its two pinned staging buffers (see _sync_ptrs). masters: the pointer tuples carry a sixth entry,
+    the fp32 master parameter address (AdamW(master_weights=True)); these go to a second device table, "masters"
+    [n], behind the first in the same buffer."""
     chunk = int(_lib.load().pico_adamw_chunk_elems())
     sizes = torch.tensor(numels, dtype=torch.int64)
     chunks = torch.tensor([(i, c) for i, n in enumerate(numels) for c in range(0, n, chunk)],
                           dtype=torch.int64).reshape(-1, 2)
-    return {"tens": torch.empty((len(numels), 5), dtype=torch.int64, device=dev), "sizes": sizes.to(dev),
-            "chunks": chunks.to(dev), "chunks_host": chunks, "n_chunks": chunks.shape[0], "ptrs": None, "turn": 0,
-            "host": [torch.empty((len(numels), 5), dtype=torch.int64).pin_memory() for _ in range(2)],
+    n = len(numels)
+    buf = torch.empty(n * (6 if masters else 5), dtype=torch.int64, device=dev)  # one upload: [n][5], then [n]
+    return {"buf": buf, "tens": buf[:5 * n].view(n, 5), "masters": buf[5 * n:] if masters else None,
+            "sizes": sizes.to(dev), "chunks": chunks.to(dev), "chunks_host": chunks, "n_chunks": chunks.shape[0],
+            "ptrs": None, "turn": 0, "host": [torch.empty_like(buf, device="cpu").pin_memory() for _ in range(2)],
             "done": [None, None], "norm": None}
 
 
@@ -52,8 +59,11 @@ def _sync_ptrs(ent, ptrs, dev):
         i = ent["turn"]
         if ent["done"][i] is not None:  # this staging buffer may still be feeding its previous copy
             ent["done"][i].synchronize()
-        ent["host"][i].numpy()[:] = ptrs
-        ent["tens"].copy_(ent["host"][i], non_blocking=True)
+        n, host = len(ptrs), ent["host"][i].numpy()
+        host[:5 * n].reshape(n, 5)[:] = [t[:5] for t in ptrs]
+        if ent["masters"] is not None:
+            host[5 * n:] = [t[5] for t in ptrs]
+        ent["buf"].copy_(ent["host"][i], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
         ent["done"][i] = ev
@@ -216,14 +226,24 @@ class AdamW(torch.optim.Optimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
                  maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
-                 max_grad_norm=None, grad_norm_groups=None):
+                 max_grad_norm=None, grad_norm_groups=None, master_weights=False):
         """max_grad_norm (an extension; None: off, the step runs exactly as without it): clip the global L2
         gradient norm inside the step. One norm over every parameter that has a gradient (all param groups and
         step counts; `grad_norm_groups`: the `groups` of clip_grad_norm_), then pico_adamw_bf16_clip scales each
         gradient as it loads it — bit-identical to clip_grad_norm_ followed by the plain step, without the
         gradient write and re-read. `self.grad_norm` is the pre-clip norm (0-dim device tensor) after each step.
         The host never reads the norm: when it is not finite the kernel writes nothing (parameters and moments
-        stay as they were) but the per-parameter `step` counters have already advanced; watch `grad_norm`."""
+        stay as they were) but the per-parameter `step` counters have already advanced; watch `grad_norm`.
+
+        master_weights (an extension; False: the bf16 step above, untouched): fp32 master weights and fp32 Adam
+        moments under the bf16 model, the Megatron / DeepSpeed / torch-AMP arrangement, still one launch
+        (pico_adamw_master; with max_grad_norm, the clip folded in). `state[p]` holds `master_param` (created at the
+        parameter's first step as `p.float()`, exact), `exp_avg` and `exp_avg_sq`, all fp32: 12 bytes of state per
+        parameter instead of 4. The update is ATen's fused AdamW on the fp32 tensors with the bf16 gradient values;
+        the bf16 parameter is overwritten in place with bf16(master) and never read, so a parameter written from
+        outside (model.load_state_dict after the first step) is overridden by its master at the next step unless
+        sync_master_params() is called. state_dict() / load_state_dict() keep the fp32 state fp32; a checkpoint of
+        the bf16 form loads too (moments upcast exactly, masters created from the parameters at the next step)."""
         if amsgrad or maximize or capturable or differentiable:
             raise NotImplementedError("picotron_amd.optim.AdamW: amsgrad / maximize / capturable / differentiable")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
@@ -236,6 +256,7 @@ class AdamW(torch.optim.Optimizer):
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.grad_norm_groups = grad_norm_groups
         self.grad_norm = None
+        self.master_weights = bool(master_weights)  # not a param-group default: state_dict() reports torch's keys
         # per (group, parameter set): device tables of sizes / 64 Ki-element chunks (fixed for the set) and of
         # the (param, grad, exp_avg, exp_avg_sq) pointers, re-uploaded only when a pointer changed (persistent
         # gradients: never after the first step); two pinned staging buffers used in turn
@@ -247,16 +268,17 @@ class AdamW(torch.optim.Optimizer):
         key = (gi, tuple((p.data_ptr(), p.numel()) for p in params))
         ent = self._tables.get(key)
         if ent is None:
-            ent = _new_tables([p.numel() for p in params], params[0].device)
+            ent = _new_tables([p.numel() for p in params], params[0].device, masters=self.master_weights)
             if len(self._tables) > 64:  # parameter sets keep changing (step counts diverging): keep the map small
                 self._tables.clear()
             self._tables[key] = ent
         ptrs = []
         for p in params:
             g32 = _deferred_grad(p)
+            st = self.state[p]
             ptrs.append((p.data_ptr(), (g32 if g32 is not None else p.grad).data_ptr(),
-                         self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
-                         0 if g32 is None else 1))
+                         st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), 0 if g32 is None else 1)
+                        + ((st["master_param"].data_ptr(),) if self.master_weights else ()))
         _sync_ptrs(ent, ptrs, params[0].device)
         return ent
 
@@ -290,6 +312,16 @@ class AdamW(torch.optim.Optimizer):
                                 f"got {p.dtype} / {p.grad.dtype} on {p.device}")
             if p.grad.is_sparse or not p.grad.is_contiguous() or not p.is_contiguous():
                 raise ValueError("picotron_amd.optim.AdamW: dense contiguous parameters and gradients only")
+        if self.master_weights:  # fp32 state only: a state of another dtype was not loaded through load_state_dict
+            for p in params:
+                for key in ("exp_avg", "exp_avg_sq", "master_param"):
+                    t = self.state[p].get(key)
+                    if t is not None and (t.dtype != torch.float32 or t.device != p.device or t.shape != p.shape
+                                          or not t.is_contiguous()):
+                        raise TypeError(f"picotron_amd.optim.AdamW(master_weights=True): state '{key}' must be a "
+                                        f"contiguous fp32 tensor of the parameter's shape and device, got {t.dtype} "
+                                        f"{tuple(t.shape)} on {t.device}")
+        state_dtype = torch.float32 if self.master_weights else None
         # per-parameter step counts, as torch.optim.AdamW keeps them: a parameter that had no gradient on
         # some steps (frozen for a while, an idle pipeline stage) advances only when it has one; one
         # launch per distinct step count. `step` stays a CPU scalar (a loaded state may carry it on the
@@ -299,10 +331,12 @@ class AdamW(torch.optim.Optimizer):
             st = self.state[p]
             if not st:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg"] = torch.zeros_like(p, dtype=state_dtype, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, dtype=state_dtype, memory_format=torch.preserve_format)
             elif st["step"].device.type != "cpu":
                 st["step"] = st["step"].detach().to("cpu", torch.float32)
+            if self.master_weights and "master_param" not in st:  # first step, or a loaded bf16-form checkpoint
+                st["master_param"] = p.detach().float()
             st["step"] += 1
             by_step.setdefault(int(st["step"].item()), []).append(p)
         return sorted(by_step.items())
@@ -321,11 +355,57 @@ class AdamW(torch.optim.Optimizer):
             beta1, beta2 = group["betas"]
             for step, ps in self._advance(group):
                 ent = self._group_tables(gi, ps)
+                if self.master_weights:
+                    self._launch_master(lib, ent, group, step, None, _lib.stream_of(ps[0]))
+                    continue
                 _lib.check(lib.pico_adamw_bf16(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
                                                ent["n_chunks"], float(group["lr"]), float(beta1), float(beta2),
                                                float(group["eps"]), float(group["weight_decay"]), step,
                                                _lib.stream_of(ps[0])), "pico_adamw_bf16")
         return loss
+
+    def _launch_master(self, lib, ent, group, step, norm_coef, stream):
+        beta1, beta2 = group["betas"]
+        _lib.check(lib.pico_adamw_master(_lib.ptr(ent["tens"]), _lib.ptr(ent["masters"]), _lib.ptr(ent["sizes"]),
+                                         _lib.ptr(ent["chunks"]), ent["n_chunks"], float(group["lr"]), float(beta1),
+                                         float(beta2), float(group["eps"]), float(group["weight_decay"]), step,
+                                         _lib.ptr(norm_coef), stream), "pico_adamw_master")
+
+    @torch.no_grad()
+    def sync_master_params(self):
+        """Re-read every existing fp32 master from its bf16 parameter (in place: the device tables stay valid).
+        Call it after writing model weights into an already-stepped optimizer (model.load_state_dict, a manual
+        `p.copy_`): the kernel never reads the bf16 parameter, so without it the master silently wins and the next
+        step overwrites the new weights. Nothing to do before the first step or with master_weights=False."""
+        for p, st in self.state.items():
+            master = st.get("master_param")
+            if master is not None:
+                master.copy_(p.detach())
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict casts every floating-point state tensor but `step` to the
+        parameter's dtype, which would round fp32 masters and moments to bf16. With master_weights=True they are
+        taken from `state_dict` again afterwards as fp32 (fp32 input: bit for bit, own copies; the bf16 moments of
+        a bf16-form checkpoint: upcast exactly; `step` its own copy too, so an optimizer loaded from another live
+        optimizer's state_dict() shares nothing with it). master_weights=False: torch's loading, unchanged."""
+        super().load_state_dict(state_dict)
+        if not self.master_weights:
+            return
+        from itertools import chain
+        saved = chain.from_iterable(g["params"] for g in state_dict["param_groups"])
+        mine = chain.from_iterable(g["params"] for g in self.param_groups)
+        id_map = dict(zip(saved, mine))
+        for k, sv in state_dict["state"].items():
+            p = id_map.get(k)
+            if p is None or not isinstance(sv, dict):
+                continue
+            if isinstance(sv.get("step"), torch.Tensor):  # torch hands the very tensor over; _advance adds in place
+                self.state[p]["step"] = sv["step"].detach().clone()
+            for key in ("exp_avg", "exp_avg_sq", "master_param"):
+                v = sv.get(key)
+                if isinstance(v, torch.Tensor) and v.is_floating_point():
+                    t = v.detach().to(device=p.device, dtype=torch.float32)
+                    self.state[p][key] = t.clone() if t.data_ptr() == v.data_ptr() else t
 
     def _step_clipped(self, lib):
         """The step with max_grad_norm: every (group, step count) table set first, one global norm over all of
@@ -341,6 +421,9 @@ class AdamW(torch.optim.Optimizer):
         sums = [_sqnorm(lib, ent, select_norm_params(ps, tp_rank, tp_world), stream) for _, _, ps, ent in work]
         nc = _norm_coef(lib, sums, groups, self.max_grad_norm, stream)
         for group, step, ps, ent in work:
+            if self.master_weights:
+                self._launch_master(lib, ent, group, step, nc, stream)
+                continue
             beta1, beta2 = group["betas"]
             _lib.check(lib.pico_adamw_bf16_clip(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
                                                 ent["n_chunks"], float(group["lr"]), float(beta1), float(beta2),
