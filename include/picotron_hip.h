@@ -33,6 +33,9 @@
  *   pico_adamw_bf16_sr, pico_sr_round_bf16
  *                             <- the bf16 step with stochastically rounded stores (torchao / optimi
  *                                 bf16_stochastic_round; no reference call), and the rounding alone
+ *   pico_muon_momentum / _normalize / _update
+ *                             <- the elementwise half of torch.optim.Muon's step (no reference call: the
+ *                                 reference trains with AdamW alone)
  *   pico_sort_ids             <- the stable id sort inside F.embedding's backward (ref picotron/model.py:223-224)
  *   pico_embedding_bwd        <- backward of F.embedding (ref picotron/model.py:223-224) + the micro-batch
  *                                 gradient accumulation (data_parallel.py:131 / autograd's grad += dW)
@@ -339,6 +342,33 @@ int pico_adamw_bf16_sr(const int64_t* tensors, const int64_t* ids, const int64_t
  * n < 2^35, 0 <= step, id < 2^32, quantity 0..2. Timed under PICO_K_CAST. */
 int pico_sr_round_bf16(const float* src, void* dst, int64_t n, uint64_t seed, int64_t step, int64_t id, int quantity,
                        void* stream);
+
+/* ---- Muon's elementwise passes over a whole list of bf16 matrices, on pico_adamw_bf16's device tables ----
+ * torch.optim.Muon's rounding points (fp32 arithmetic, each named result rounded once to bf16, nearest even); the
+ * Newton-Schulz GEMMs between pico_muon_normalize and pico_muon_update are the caller's (hipBLASLt).
+ * tensors: device int64 [n_tensors][5] = (param, grad, momentum_buffer, work addresses, grad_is_f32), so
+ * pico_grad_sqnorm / pico_grad_scale work on it unchanged; work: the tensor's bf16 slice of the Newton-Schulz input
+ * buffer. sizes / chunks as pico_adamw_bf16. The gradient value g is the AdamW kernels' (bf16 .grad, or
+ * bf16(main_grad) when grad_is_f32). lerp(a, b, w) is ATen's: |w| < 0.5 ? a + w (b - a) : b - (b - a)(1 - w), w
+ * cast to fp32. No atomics: the same inputs give the same bits on every run. All timed under PICO_K_ADAMW.
+ * pico_muon_momentum: m' = bf16(lerp(m, g, 1 - momentum)) -> momentum_buffer; u = bf16(lerp(g, m', momentum)) when
+ * nesterov, else m', -> work; partials[c] (device float [n_chunks]) = the fp32 sum of squares of the bf16 u values
+ * of chunk c, in pico_grad_sqnorm's summation order. 8 bytes per element (10 with an fp32 main_grad). */
+int pico_muon_momentum(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
+                       double momentum, int nesterov, float* partials, void* stream);
+/* Two launches. norms[t] (device float [n_tensors]) = max(float(bf16(sqrt(s_t))), (float)eps), s_t = partials[
+ * chunk_start[t] .. chunk_start[t + 1]) added in index order in double: torch's bf16 norm().clamp(min=eps).
+ * chunk_start: device int64 [n_tensors + 1], the first chunk of each tensor (chunks holds each tensor's chunks
+ * together, tensors in order). Then work = bf16(work / norms[t]) in place, a true division. 4 bytes per element. */
+int pico_muon_normalize(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
+                        const int64_t* chunk_start, int64_t n_tensors, const float* partials, double eps,
+                        float* norms, void* stream);
+/* p = bf16(p * (float)(1 - lr * weight_decay)), then p = bf16(p + (float)(-(lr * ratios[t])) * O): torch's mul_
+ * followed by add_(O, alpha=-adjusted_lr), two roundings, the scalars formed in double. out_ptrs: device int64
+ * [n_tensors], the address of each tensor's O (bf16, contiguous, the parameter's shape); ratios: device double
+ * [n_tensors], torch's _adjust_lr ratio of each shape. 6 bytes per element. */
+int pico_muon_update(const int64_t* tensors, const int64_t* out_ptrs, const int64_t* sizes, const int64_t* chunks,
+                     int64_t n_chunks, double lr, double weight_decay, const double* ratios, void* stream);
 
 /* ---- softmax cross-entropy (mean over non-ignored rows) ----
  * logits: [rows, vocab] bf16, row stride ld (elements); target: [rows] int64.

@@ -107,6 +107,9 @@ _SIGNATURES = {
     "pico_grad_sqnorm": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pico_grad_clip_coef": (ctypes.c_int, [c_vp, ctypes.c_double, c_vp, c_vp]),
     "pico_grad_scale": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "pico_muon_momentum": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_int, c_vp, c_vp]),
+    "pico_muon_normalize": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_double, c_vp, c_vp]),
+    "pico_muon_update": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double, c_vp, c_vp]),
     "pico_cross_entropy_fwd": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "pico_cross_entropy_fwd_grad": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "pico_ce_count": (ctypes.c_int, [c_vp, c_i64, c_i64, ctypes.c_float, c_vp, c_vp]),

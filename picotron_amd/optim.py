@@ -20,6 +20,10 @@ mixed-precision recipes' arrangement, on the same tables and in the same one lau
 `AdamW(stochastic_rounding=True)` (pico_adamw_bf16_sr): the bf16 step with the parameter and both moments rounded
 stochastically from a counter-based generator: small updates and slow decays survive on average at the bf16 step's
 state size and traffic.
+
+`Muon` (csrc/muon.hip): torch.optim.Muon for the 2-D hidden matrices on the same tables: three whole-list HIP kernels
+(momentum, normalise, update) around the Newton-Schulz GEMMs; `muon_param_split` picks the
+matrices Muon takes from a Llama and leaves the rest to AdamW.
 """
 import math
 
@@ -43,8 +47,8 @@ def _new_tables(numels, dev, sixth=None):
     """Device tables of one parameter set: sizes / 64 Ki-element chunks (fixed for the set) and the [n][5] pointer
     table with its two pinned staging buffers (see _sync_ptrs). sixth: the pointer tuples carry a sixth entry, which
     goes to a second device table [n] of that name behind the first in the same buffer: "masters", the fp32 master
-    parameter address (AdamW(master_weights=True)), or "ids", the generator's tensor id
-    (AdamW(stochastic_rounding=True))."""
+    parameter address (AdamW(master_weights=True)), "ids", the generator's tensor id
+    (AdamW(stochastic_rounding=True)), or "out", the address of the orthogonalised update (Muon)."""
     chunk = int(_lib.load().pico_adamw_chunk_elems())
     sizes = torch.tensor(numels, dtype=torch.int64)
     chunks = torch.tensor([(i, c) for i, n in enumerate(numels) for c in range(0, n, chunk)],
@@ -52,7 +56,7 @@ def _new_tables(numels, dev, sixth=None):
     n = len(numels)
     buf = torch.empty(n * (6 if sixth else 5), dtype=torch.int64, device=dev)  # one upload: [n][5], then [n]
     return {"buf": buf, "tens": buf[:5 * n].view(n, 5), "masters": buf[5 * n:] if sixth == "masters" else None,
-            "ids": buf[5 * n:] if sixth == "ids" else None,
+            "ids": buf[5 * n:] if sixth == "ids" else None, "out": buf[5 * n:] if sixth == "out" else None,
             "sizes": sizes.to(dev), "chunks": chunks.to(dev), "chunks_host": chunks, "n_chunks": chunks.shape[0],
             "ptrs": None, "turn": 0, "host": [torch.empty_like(buf, device="cpu").pin_memory() for _ in range(2)],
             "done": [None, None], "norm": None}
@@ -67,7 +71,7 @@ def _sync_ptrs(ent, ptrs, dev):
             ent["done"][i].synchronize()
         n, host = len(ptrs), ent["host"][i].numpy()
         host[:5 * n].reshape(n, 5)[:] = [t[:5] for t in ptrs]
-        if host.size > 5 * n:  # the sixth entries: masters or ids
+        if host.size > 5 * n:  # the sixth entries: masters, ids or out
             host[5 * n:] = [t[5] for t in ptrs]
         ent["buf"].copy_(ent["host"][i], non_blocking=True)
         ev = torch.cuda.Event()
@@ -493,3 +497,234 @@ class AdamW(torch.optim.Optimizer):
                                                 float(group["eps"]), float(group["weight_decay"]), step,
                                                 _lib.ptr(nc), stream), "pico_adamw_bf16_clip")
         self.grad_norm = nc[0]
+
+
+# ---- Muon ----
+
+def muon_param_split(model):
+    """(muon_params, other_params) of a Llama (picotron_amd.model): Muon takes the 2-D hidden matrices, i.e. the
+    parameters with ndim == 2 whose name starts with `decoder_layers.`; everything else (the embedding, final_proj
+    and all norms) is AdamW's. Every parameter lands in exactly one list, in named_parameters() order."""
+    muon, other = [], []
+    for name, p in model.named_parameters():
+        (muon if p.ndim == 2 and name.startswith("decoder_layers.") else other).append(p)
+    return muon, other
+
+
+def _muon_ratio(adjust_lr_fn, shape):
+    """torch.optim._muon._adjust_lr's ratio (double): adjusted_lr = lr * ratio."""
+    A, B = shape
+    if adjust_lr_fn is None or adjust_lr_fn == "original":
+        return math.sqrt(max(1, A / B))
+    if adjust_lr_fn == "match_rms_adamw":
+        return 0.2 * math.sqrt(max(A, B))
+    raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+
+
+def _muon_layout(shapes, adjust_lr_fn=None):
+    """The host half of Muon's tables for matrices of `shapes`, in list order: `chunk_start` ([n + 1], the first
+    64 Ki-element chunk of each tensor), `ratios` (torch's _adjust_lr ratio of each), `buckets` ({shape: tensor
+    indices}, shapes in order of first appearance: a bucket's Newton-Schulz inputs are one [L, A, B] buffer) and
+    `slot` (each tensor's (shape, position in its bucket))."""
+    chunk = int(_lib.load().pico_adamw_chunk_elems())
+    shapes = [tuple(int(d) for d in s) for s in shapes]
+    chunk_start = [0]
+    for a, b in shapes:
+        chunk_start.append(chunk_start[-1] + (a * b + chunk - 1) // chunk)
+    buckets, slot = {}, []
+    for i, s in enumerate(shapes):
+        idx = buckets.setdefault(s, [])
+        slot.append((s, len(idx)))
+        idx.append(i)
+    return {"shapes": shapes, "chunk_start": chunk_start, "ratios": [_muon_ratio(adjust_lr_fn, s) for s in shapes],
+            "buckets": buckets, "slot": slot}
+
+
+def _muon_work(layout, dev):
+    """The Newton-Schulz input buffers of a layout: ({shape: [L, A, B] bf16 buffer}, each tensor's slice of its
+    bucket's buffer, in list order): 2 bytes per Muon parameter."""
+    bufs = {s: torch.empty((len(idx),) + s, dtype=torch.bfloat16, device=dev) for s, idx in layout["buckets"].items()}
+    return bufs, [bufs[s][k] for s, k in layout["slot"]]
+
+
+def _muon_ns_plan(layout, slices, dev):
+    """The persistent Newton-Schulz workspace, sized for the largest matrix and shared by all: two ping-pong
+    buffers and the two Gram buffers (G, G2); and per matrix the views the GEMMs take (X: the matrix's slice of the
+    work buffer, where the result lands again)."""
+    pp = max(s[0] * s[1] for s in layout["shapes"])
+    gg = max(min(s) ** 2 for s in layout["shapes"])
+    flat = [torch.empty(n, dtype=torch.bfloat16, device=dev) for n in (pp, pp, gg, gg)]
+    plan = []
+    for s, x in zip(layout["shapes"], slices):
+        m = min(s)
+        plan.append({"X": x, "P": [flat[0][:s[0] * s[1]].view(s), flat[1][:s[0] * s[1]].view(s)],
+                     "G": flat[2][:m * m].view(m, m), "G2": flat[3][:m * m].view(m, m), "tall": s[0] > s[1]})
+    return flat, plan
+
+
+def _newton_schulz(plan, coefficients, ns_steps):
+    """ns_steps times G = X X^T, G2 = b G + c G G, X = a X + G2 X per matrix, as bf16 GEMMs (torch.mm /
+    torch.addmm, the calls torch's Muon makes) into the plan's buffers. A tall matrix [A, B] (A > B) is iterated as
+    it lies, without a transposed copy: with Y = X^T the same sums read G = Y^T Y, Y = a Y + Y G2^T, the GEMM
+    taking the transposes. The result is left in X, contiguous in the parameter's layout."""
+    a, b, c = coefficients
+    for sb in plan:
+        X, (P0, P1), G, G2 = sb["X"], sb["P"], sb["G"], sb["G2"]
+        cur = X
+        for k in range(ns_steps):
+            nxt = X if (k == ns_steps - 1 and cur is not X) else (P1 if cur is P0 else P0)
+            if sb["tall"]:
+                torch.mm(cur.T, cur, out=G)
+                torch.addmm(G, G, G, beta=b, alpha=c, out=G2)
+                torch.addmm(cur, cur, G2.T, beta=a, out=nxt)
+            else:
+                torch.mm(cur, cur.T, out=G)
+                torch.addmm(G, G, G, beta=b, alpha=c, out=G2)
+                torch.addmm(cur, G2, cur, beta=a, out=nxt)
+            cur = nxt
+        if cur is not X:  # ns_steps == 1: a GEMM cannot write over its own input
+            X.copy_(cur)
+
+
+class Muon(torch.optim.Optimizer):
+    """torch.optim.Muon on the gfx950 kernels of csrc/muon.hip, for bf16 matrices on a HIP device: torch's positional
+    signature and defaults, the same `param_groups` keys and the same `state[p]` layout (`momentum_buffer` only, in
+    the parameter dtype, no step counter), so state_dict() / load_state_dict() interchange with torch.optim.Muon.
+
+    Per matrix p [A, B], with g the bf16 gradient (or bf16(main_grad) of DataParallelBucket(defer_grad_cast=True),
+    read in place) and m the momentum buffer, fp32 arithmetic and one bf16 rounding (nearest even) per named result,
+    torch's rounding points:
+      m' = bf16(lerp(m, g, 1 - momentum));  u = bf16(lerp(g, m', momentum)) if nesterov else m'
+      X0 = bf16(u / max(float(bf16(||u||)), eps))                  (a true division)
+      O  = ns_steps Newton-Schulz iterations on X0 (its transposed view when A > B), bf16 GEMMs
+      p  = bf16(p * (1 - lr weight_decay));  p = bf16(p - lr ratio O),  ratio = torch's _adjust_lr(shape)
+    One deliberate difference from torch 2.10: with nesterov=False and a bf16 gradient, torch's `.bfloat16()` is a
+    no-op, so its in-place `div_` normalises the momentum buffer itself (after a step the stored buffer has norm 1).
+    Here the buffer keeps m', as the documented algorithm has it.
+
+    step(): per parameter group, over the parameters that have a gradient, pico_muon_momentum and pico_muon_normalize
+    (whole list), the Newton-Schulz GEMMs per matrix (torch.mm / torch.addmm on hipBLASLt, the calls torch's Muon
+    makes, into persistent buffers), then one pico_muon_update: 4 HIP launches plus 3 * ns_steps GEMM calls per
+    matrix. Nothing is read on the host and nothing is allocated after the first step of a parameter set. Workspace:
+    2 bytes per Muon parameter (the Newton-Schulz inputs, one [L, A, B] buffer per matrix shape, where the results
+    land too) plus two ping-pong and two Gram buffers of the largest matrix. (Batching a shape's matrices into
+    bmm / baddbmm calls is not in: DESIGN.md §4j.)
+
+    Refused: parameters that are not 2-D (ValueError, at construction); a parameter tagged `_pico_tp_sharded`
+    (NotImplementedError: orthogonalising a shard is not Muon); a tensor lr; at step(), before any state is touched,
+    parameters or gradients that are not contiguous bf16 HIP tensors (TypeError / ValueError). Gradient clipping:
+    the standalone clip_grad_norm_ in front of the step."""
+    reads_deferred_grads = True  # as AdamW: the fp32 main_grad of DataParallelBucket(defer_grad_cast=True) is read in place
+
+    def __init__(self, params, lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
+                 ns_coefficients=(3.4445, -4.7750, 2.0315), eps=1e-7, ns_steps=5, adjust_lr_fn=None):
+        if isinstance(lr, torch.Tensor):
+            raise TypeError("picotron_amd.optim.Muon: a float lr only")
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"momentum should be >= 0 but is: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
+        if not 0.0 <= eps:
+            raise ValueError(f"eps should be >= 0 but is: {eps}")
+        if adjust_lr_fn is not None and adjust_lr_fn not in ("original", "match_rms_adamw"):
+            raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+        defaults = {"lr": lr, "weight_decay": weight_decay, "momentum": momentum, "nesterov": nesterov,
+                    "ns_coefficients": ns_coefficients, "eps": eps, "ns_steps": ns_steps, "adjust_lr_fn": adjust_lr_fn}
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.ndim != 2:
+                    raise ValueError(f"Muon only supports 2D parameters whereas we found a parameter with size: "
+                                     f"{p.size()}")
+                if getattr(p, "_pico_tp_sharded", False):
+                    raise NotImplementedError("picotron_amd.optim.Muon: a tensor-parallel shard is not a matrix to "
+                                              "orthogonalise (Newton-Schulz sharded across ranks is not implemented)")
+        self._tables = {}  # per (group, parameter set): the device tables and the Newton-Schulz workspace
+
+    def _validate(self, group):
+        """The group's parameters that have a gradient, everything checked before any state is touched."""
+        params = [p for p in group["params"] if p.grad is not None]
+        if not params:
+            return params
+        if isinstance(group["lr"], torch.Tensor):
+            raise TypeError("picotron_amd.optim.Muon: a float lr only")
+        if not 0 <= int(group["ns_steps"]) < 100:
+            raise ValueError("Number of steps must be less than 100 for computational efficiency")
+        if len(group["ns_coefficients"]) != 3:
+            raise ValueError("Coefficients must be a tuple of exactly 3 values")
+        _muon_ratio(group["adjust_lr_fn"], (1, 1))
+        for p in params:
+            if not (p.is_cuda and p.dtype == torch.bfloat16 and p.grad.dtype == torch.bfloat16 and p.grad.is_cuda):
+                raise TypeError("picotron_amd.optim.Muon: parameters and gradients must be bf16 HIP tensors, "
+                                f"got {p.dtype} / {p.grad.dtype} on {p.device}")
+            if p.grad.is_sparse or not p.grad.is_contiguous() or not p.is_contiguous():
+                raise ValueError("picotron_amd.optim.Muon: dense contiguous parameters and gradients only")
+            if p.ndim != 2 or p.grad.shape != p.shape:
+                raise ValueError("picotron_amd.optim.Muon: 2-D parameters with gradients of their shape only")
+            _deferred_grad(p)
+            m = self.state[p].get("momentum_buffer") if p in self.state else None
+            if m is not None and (m.dtype != torch.bfloat16 or m.device != p.device or m.shape != p.shape
+                                  or not m.is_contiguous()):
+                raise TypeError("picotron_amd.optim.Muon: state 'momentum_buffer' must be a contiguous bf16 tensor of "
+                                f"the parameter's shape and device, got {m.dtype} {tuple(m.shape)} on {m.device}")
+        return params
+
+    def _group_tables(self, gi, group, params):
+        dev = params[0].device
+        key = (gi, tuple((p.data_ptr(), tuple(p.shape)) for p in params), group["adjust_lr_fn"])
+        ent = self._tables.get(key)
+        if ent is None:
+            layout = _muon_layout([p.shape for p in params], group["adjust_lr_fn"])
+            ent = _new_tables([p.numel() for p in params], dev, "out")
+            bufs, slices = _muon_work(layout, dev)
+            flat, plan = _muon_ns_plan(layout, slices, dev)
+            ent.update(layout=layout, work=bufs, slices=slices, ns_flat=flat, ns_plan=plan,
+                       chunk_start=torch.tensor(layout["chunk_start"], dtype=torch.int64).to(dev),
+                       ratios=torch.tensor(layout["ratios"], dtype=torch.float64).to(dev),
+                       partials=torch.empty(max(ent["n_chunks"], 1), dtype=torch.float32, device=dev),
+                       norms=torch.empty(len(params), dtype=torch.float32, device=dev))
+            if len(self._tables) > 16:  # parameter sets keep changing: keep the map (and its workspaces) small
+                self._tables.clear()
+            self._tables[key] = ent
+        ptrs = []
+        for p, w in zip(params, ent["slices"]):
+            g32 = _deferred_grad(p)
+            # the orthogonalised update lands where its input was: the tensor's slice of the work buffer
+            ptrs.append((p.data_ptr(), (g32 if g32 is not None else p.grad).data_ptr(),
+                         self.state[p]["momentum_buffer"].data_ptr(), w.data_ptr(), 0 if g32 is None else 1,
+                         w.data_ptr()))
+        _sync_ptrs(ent, ptrs, dev)
+        return ent
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        work = [(gi, group, self._validate(group)) for gi, group in enumerate(self.param_groups)]
+        for gi, group, params in work:
+            if not params:
+                continue
+            for p in params:
+                st = self.state[p]
+                if "momentum_buffer" not in st:
+                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            ent = self._group_tables(gi, group, params)
+            stream = _lib.stream_of(params[0])
+            tens, sizes, chunks, n_chunks = (_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
+                                             ent["n_chunks"])
+            _lib.check(lib.pico_muon_momentum(tens, sizes, chunks, n_chunks, float(group["momentum"]),
+                                              1 if group["nesterov"] else 0, _lib.ptr(ent["partials"]), stream),
+                       "pico_muon_momentum")
+            _lib.check(lib.pico_muon_normalize(tens, sizes, chunks, n_chunks, _lib.ptr(ent["chunk_start"]),
+                                               len(params), _lib.ptr(ent["partials"]), float(group["eps"]),
+                                               _lib.ptr(ent["norms"]), stream), "pico_muon_normalize")
+            _newton_schulz(ent["ns_plan"], group["ns_coefficients"], int(group["ns_steps"]))
+            _lib.check(lib.pico_muon_update(tens, _lib.ptr(ent["out"]), sizes, chunks, n_chunks, float(group["lr"]),
+                                            float(group["weight_decay"]), _lib.ptr(ent["ratios"]), stream),
+                       "pico_muon_update")
+        return loss
