@@ -10,8 +10,13 @@
 //   p -= lr * wd * p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;
 //   p -= (float)(lr / bc1) * m / (float)(sqrt(v) / sqrt(bc2) + eps),  bc_i = 1 - b_i^step (host, double).
 // Bytes per element: 8 read (p, g, m, v) + 6 written (p, m, v) for bf16 (10 read with an fp32 main_grad).
-// pico_adamw_master (below) keeps an fp32 master copy of each parameter and fp32 moments: 28 bytes per element.
+// pico_adamw_master keeps an fp32 master copy of each parameter and fp32 moments: 28 bytes per element.
+//
+// One kernel template covers the six forms: where p, m, v live is a state policy (Bf16State<SR>, MasterState),
+// everything else (chunk bounds, vector / scalar choice, gradient load, clip, adam_elem) is adamw_chunk's.
 #include "optim_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -30,122 +35,196 @@ PICO_DEV void adam_elem(float& p, float g, float& m, float& v, const AdamHyper& 
   p -= h.step_size * m / denom;
 }
 
-// The device tables and load_grad8 (the fp32 main_grad form, grad_is_f32 = 1) are in optim_common.h.
-// CLIP: the gradient is first scaled by the clip coefficient and rounded to bf16, g = bf16(g * coef): the value
-// pico_grad_scale would have stored, so the step is bit-identical to scale-then-step without the gradient
-// write and re-read (coef = 1: g unchanged, bit-identical to the plain step).
-// SR: the three stores round stochastically (f2bf_sr, optim_common.h) instead of to nearest even; quantity 0, 1, 2
-// = parameter, exp_avg, exp_avg_sq. The vector path draws the 8 elements' bits with one Philox call per quantity;
-// the scalar path evaluates the same calls and takes its lane, so both paths store the same bits.
-template <bool GF32, bool CLIP, bool SR>
-PICO_DEV void adamw_chunk(bf16_t* p, const void* g, bf16_t* m, bf16_t* v, int64_t n, int64_t c0, const AdamHyper& h,
-                          float coef, const SrKey& sr, uint32_t id) {
+// A state policy holds the pointers of one tensor and gives adamw_chunk: vec_ok() (may 8 elements move with
+// 16-byte accesses), load8 / store8 of a lane's 8 elements through its own register type Vec8 with get / put of
+// element j in place, and load1 / store1 of one element. Each keeps the registers in the layout they are loaded in
+// (handing the walker float[8] copies instead costs the master kernel its 6th wave: DESIGN.md §4k).
+//
+// p, m, v in bf16, as torch keeps the states of a bf16 parameter. SR: the three stores round stochastically
+// (f2bf_sr, optim_common.h) instead of to nearest even; quantity 0, 1, 2 = parameter, exp_avg, exp_avg_sq. The
+// vector path draws the 8 elements' bits with one Philox call per quantity; the scalar path evaluates the same
+// calls and takes its lane, so both paths store the same bits. id: the generator's tensor id.
+template <bool SR>
+struct Bf16State {
+  bf16_t *p, *m, *v;
+  SrKey sr;
+  uint32_t id;
+  typedef uint32_t Words[4];  // SR only: the random bits of the 8 elements around an index, for one quantity
+  struct Vec8 {
+    u16x8 p, m, v;
+    Words wp, wm, wv;
+  };
+
+  PICO_DEV Bf16State(const int64_t* t, const int64_t* ids, int64_t ti, const SrKey& key)
+      : p((bf16_t*)t[0]), m((bf16_t*)t[2]), v((bf16_t*)t[3]), sr(key), id(SR ? (uint32_t)ids[ti] : 0) {}
+
+  PICO_DEV bool vec_ok() const { return (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0; }
+
+  PICO_DEV void draw(int64_t i, Words& wp, Words& wm, Words& wv) const {
+    if constexpr (SR) {
+      sr_words(sr, id, i, 0, wp);
+      sr_words(sr, id, i, 1, wm);
+      sr_words(sr, id, i, 2, wv);
+    }
+  }
+  PICO_DEV static unsigned short round(float x, const Words& w, int j) {
+    if constexpr (SR) return f2bf_sr(__float_as_uint(x), sr_lane(w, j));
+    else return f2bf(x);
+  }
+  PICO_DEV void load8(int64_t i, Vec8& r) const {
+    r.p = *reinterpret_cast<const u16x8*>(p + i);
+    r.m = *reinterpret_cast<const u16x8*>(m + i);
+    r.v = *reinterpret_cast<const u16x8*>(v + i);
+    draw(i, r.wp, r.wm, r.wv);
+  }
+  PICO_DEV void get(const Vec8& r, int j, float& pf, float& mf, float& vf) const {
+    pf = bf2f(r.p[j]);
+    mf = bf2f(r.m[j]);
+    vf = bf2f(r.v[j]);
+  }
+  PICO_DEV void put(Vec8& r, int j, float pf, float mf, float vf) const {
+    r.p[j] = round(pf, r.wp, j);
+    r.m[j] = round(mf, r.wm, j);
+    r.v[j] = round(vf, r.wv, j);
+  }
+  PICO_DEV void store8(int64_t i, const Vec8& r) const {
+    *reinterpret_cast<u16x8*>(p + i) = r.p;
+    *reinterpret_cast<u16x8*>(m + i) = r.m;
+    *reinterpret_cast<u16x8*>(v + i) = r.v;
+  }
+  PICO_DEV void load1(int64_t i, float& pf, float& mf, float& vf) const {
+    pf = bf2f(p[i]);
+    mf = bf2f(m[i]);
+    vf = bf2f(v[i]);
+  }
+  PICO_DEV void store1(int64_t i, float pf, float mf, float vf) const {
+    Words wp, wm, wv;
+    draw(i, wp, wm, wv);
+    const int j = (int)(i & 7);
+    p[i] = round(pf, wp, j);
+    m[i] = round(mf, wm, j);
+    v[i] = round(vf, wv, j);
+  }
+};
+
+// fp32 master weights and fp32 moments under the bf16 model parameter (pico_adamw_master): adam_elem runs on the
+// fp32 master p32 and the fp32 m, v, which are stored as fp32: ATen's fused AdamW on fp32 tensors. The bf16 model
+// parameter is bf16(p32), written and never read. Bytes per element: 14 read (p32, g, m, v) + 14 written (p32, m,
+// v, p), 16 read with an fp32 main_grad. Vector path: two 16-byte accesses per fp32 operand and one per bf16
+// operand (fp32 pointers 32-byte aligned, the rule of grad_vec_ok<true>).
+struct MasterState {
+  bf16_t* p;
+  float *p32, *m, *v;
+  struct Vec8 {
+    f32x4 p[2], m[2], v[2];
+    u16x8 pb;
+  };
+
+  PICO_DEV MasterState(const int64_t* t, const int64_t* masters, int64_t ti, const SrKey&)
+      : p((bf16_t*)t[0]), p32((float*)masters[ti]), m((float*)t[2]), v((float*)t[3]) {}
+
+  PICO_DEV bool vec_ok() const {
+    return (((uintptr_t)p & 15) == 0) && ((((uintptr_t)p32 | (uintptr_t)m | (uintptr_t)v) & 31) == 0);
+  }
+  PICO_DEV void load8(int64_t i, Vec8& r) const {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      r.p[k] = reinterpret_cast<const f32x4*>(p32 + i)[k];
+      r.m[k] = reinterpret_cast<const f32x4*>(m + i)[k];
+      r.v[k] = reinterpret_cast<const f32x4*>(v + i)[k];
+    }
+  }
+  PICO_DEV void get(const Vec8& r, int j, float& pf, float& mf, float& vf) const {
+    pf = r.p[j / 4][j % 4];
+    mf = r.m[j / 4][j % 4];
+    vf = r.v[j / 4][j % 4];
+  }
+  PICO_DEV void put(Vec8& r, int j, float pf, float mf, float vf) const {
+    r.p[j / 4][j % 4] = pf;
+    r.m[j / 4][j % 4] = mf;
+    r.v[j / 4][j % 4] = vf;
+    r.pb[j] = f2bf(pf);
+  }
+  PICO_DEV void store8(int64_t i, const Vec8& r) const {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      reinterpret_cast<f32x4*>(p32 + i)[k] = r.p[k];
+      reinterpret_cast<f32x4*>(m + i)[k] = r.m[k];
+      reinterpret_cast<f32x4*>(v + i)[k] = r.v[k];
+    }
+    *reinterpret_cast<u16x8*>(p + i) = r.pb;
+  }
+  PICO_DEV void load1(int64_t i, float& pf, float& mf, float& vf) const {
+    pf = p32[i];
+    mf = m[i];
+    vf = v[i];
+  }
+  PICO_DEV void store1(int64_t i, float pf, float mf, float vf) const {
+    p32[i] = pf;
+    m[i] = mf;
+    v[i] = vf;
+    p[i] = f2bf(pf);
+  }
+};
+
+// One workgroup's chunk of one tensor. The gradient value is load_grad8 / load_grad1's (optim_common.h; the fp32
+// main_grad form is grad_is_f32 = 1). CLIP: it is first scaled by the clip coefficient and rounded to bf16,
+// g = bf16(g * coef): the value pico_grad_scale would have stored, so the step is bit-identical to scale-then-step
+// without the gradient write and re-read (coef = 1: g unchanged, bit-identical to the plain step).
+template <bool GF32, bool CLIP, class State>
+PICO_DEV void adamw_chunk(const State& st, const void* g, int64_t n, int64_t c0, const AdamHyper& h, float coef) {
   const int64_t end = min(n, c0 + CHUNK);
-  const bool vec = ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0) &&
-                   (((uintptr_t)g & (GF32 ? 31 : 15)) == 0) && (n % 8 == 0);
-  if (vec) {
+  if (st.vec_ok() && grad_vec_ok<GF32>(g, n)) {
     for (int64_t i = c0 + 8 * (int64_t)threadIdx.x; i < end; i += 8 * 256) {
-      u16x8 pv = *reinterpret_cast<const u16x8*>(p + i);
-      u16x8 mv = *reinterpret_cast<const u16x8*>(m + i), vv = *reinterpret_cast<const u16x8*>(v + i);
+      typename State::Vec8 r;
+      st.load8(i, r);
       float gf[8];
       load_grad8<GF32>(g, i, gf);
-      uint32_t rp[4], rm[4], rv[4];
-      if constexpr (SR) {
-        sr_words(sr, id, i, 0, rp);
-        sr_words(sr, id, i, 1, rm);
-        sr_words(sr, id, i, 2, rv);
-      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float pf = bf2f(pv[j]), mf = bf2f(mv[j]), vf = bf2f(vv[j]);
+        float pf, mf, vf;
+        st.get(r, j, pf, mf, vf);
         if constexpr (CLIP) gf[j] = bf2f(f2bf(gf[j] * coef));
         adam_elem(pf, gf[j], mf, vf, h);
-        if constexpr (SR) {
-          pv[j] = f2bf_sr(__float_as_uint(pf), sr_lane(rp, j));
-          mv[j] = f2bf_sr(__float_as_uint(mf), sr_lane(rm, j));
-          vv[j] = f2bf_sr(__float_as_uint(vf), sr_lane(rv, j));
-        } else {
-          pv[j] = f2bf(pf);
-          mv[j] = f2bf(mf);
-          vv[j] = f2bf(vf);
-        }
+        st.put(r, j, pf, mf, vf);
       }
-      *reinterpret_cast<u16x8*>(p + i) = pv;
-      *reinterpret_cast<u16x8*>(m + i) = mv;
-      *reinterpret_cast<u16x8*>(v + i) = vv;
+      st.store8(i, r);
     }
   } else {
     for (int64_t i = c0 + threadIdx.x; i < end; i += 256) {
-      float pf = bf2f(p[i]), mf = bf2f(m[i]), vf = bf2f(v[i]);
+      float pf, mf, vf;
+      st.load1(i, pf, mf, vf);
       float gf = load_grad1<GF32>(g, i);
       if constexpr (CLIP) gf = bf2f(f2bf(gf * coef));
       adam_elem(pf, gf, mf, vf, h);
-      if constexpr (SR) {
-        uint32_t rp[4], rm[4], rv[4];
-        sr_words(sr, id, i, 0, rp);
-        sr_words(sr, id, i, 1, rm);
-        sr_words(sr, id, i, 2, rv);
-        const int j = (int)(i & 7);
-        p[i] = f2bf_sr(__float_as_uint(pf), sr_lane(rp, j));
-        m[i] = f2bf_sr(__float_as_uint(mf), sr_lane(rm, j));
-        v[i] = f2bf_sr(__float_as_uint(vf), sr_lane(rv, j));
-      } else {
-        p[i] = f2bf(pf);
-        m[i] = f2bf(mf);
-        v[i] = f2bf(vf);
-      }
+      st.store1(i, pf, mf, vf);
     }
   }
 }
 
-// ids: the generator's tensor ids, [n_tensors] (SR only; null otherwise)
-template <bool CLIP, bool SR = false>
-PICO_DEV void adamw_block(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, const AdamHyper& h,
-                          float coef, const int64_t* ids = nullptr, const SrKey& sr = SrKey{}) {
-  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
-  const int64_t* t = tensors + 5 * ti;
-  bf16_t* p = (bf16_t*)t[0];
-  const void* g = (const void*)t[1];
-  bf16_t* m = (bf16_t*)t[2];
-  bf16_t* v = (bf16_t*)t[3];
-  uint32_t id = 0;
-  if constexpr (SR) id = (uint32_t)ids[ti];
-  if (t[4]) adamw_chunk<true, CLIP, SR>(p, g, m, v, sizes[ti], c0, h, coef, sr, id);
-  else adamw_chunk<false, CLIP, SR>(p, g, m, v, sizes[ti], c0, h, coef, sr, id);
-}
+enum { FORM_BF16, FORM_SR, FORM_MASTER };
 
-__global__ __launch_bounds__(256) void adamw_bf16_kernel(const int64_t* __restrict__ tensors,
-                                                         const int64_t* __restrict__ sizes,
-                                                         const int64_t* __restrict__ chunks, AdamHyper h) {
-  adamw_block<false>(tensors, sizes, chunks, h, 1.0f);
-}
-
-// norm_coef: device (gradient norm, clip coefficient), as pico_grad_clip_coef leaves them. A non-finite norm
-// (an inf / NaN gradient somewhere in the list) skips the update: nothing is written.
-__global__ __launch_bounds__(256) void adamw_bf16_clip_kernel(const int64_t* __restrict__ tensors,
-                                                              const int64_t* __restrict__ sizes,
-                                                              const int64_t* __restrict__ chunks, AdamHyper h,
-                                                              const float* __restrict__ norm_coef) {
-  const float norm = norm_coef[0], coef = norm_coef[1];
-  if (!isfinite(norm)) return;
-  adamw_block<true>(tensors, sizes, chunks, h, coef);
-}
-
-// The bf16 step with stochastically rounded stores (pico_adamw_bf16_sr): the kernels above with SR on. CLIP as
-// adamw_bf16_clip_kernel (g = bf16(g * coef), nothing written when the norm is not finite); norm_coef unused otherwise.
-template <bool CLIP>
-__global__ __launch_bounds__(256) void adamw_bf16_sr_kernel(const int64_t* __restrict__ tensors,
-                                                            const int64_t* __restrict__ ids,
-                                                            const int64_t* __restrict__ sizes,
-                                                            const int64_t* __restrict__ chunks, AdamHyper h, SrKey sr,
-                                                            const float* __restrict__ norm_coef) {
+// sixth: the masters table (FORM_MASTER) or the generator's tensor ids (FORM_SR), [n_tensors]; unused, as sr is,
+// by the other forms. CLIP: norm_coef is the device (gradient norm, clip coefficient) pair as pico_grad_clip_coef
+// leaves it; a non-finite norm (an inf / NaN gradient somewhere in the list) skips the update: nothing is written.
+template <int FORM, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_kernel(const int64_t* __restrict__ tensors,
+                                                    const int64_t* __restrict__ sixth,
+                                                    const int64_t* __restrict__ sizes,
+                                                    const int64_t* __restrict__ chunks, AdamHyper h, SrKey sr,
+                                                    const float* __restrict__ norm_coef) {
   float coef = 1.0f;
   if constexpr (CLIP) {
     const float norm = norm_coef[0];
     coef = norm_coef[1];
     if (!isfinite(norm)) return;
   }
-  adamw_block<CLIP, true>(tensors, sizes, chunks, h, coef, ids, sr);
+  using State = std::conditional_t<FORM == FORM_MASTER, MasterState, Bf16State<FORM == FORM_SR>>;
+  const OptChunk c = opt_chunk(tensors, sizes, chunks);
+  const State st(c.t, sixth, c.ti, sr);
+  const void* g = (const void*)c.t[1];
+  if (c.t[4]) adamw_chunk<true, CLIP>(st, g, c.n, c.c0, h, coef);
+  else adamw_chunk<false, CLIP>(st, g, c.n, c.c0, h, coef);
 }
 
 // pico_sr_round_bf16: the rounding alone. Aligned pointers: 8 elements per lane with one Philox call, then a scalar
@@ -174,92 +253,35 @@ __global__ __launch_bounds__(256) void sr_round_bf16_kernel(const uint32_t* __re
   }
 }
 
-// ---- fp32 master weights and fp32 moments under the bf16 model parameter (pico_adamw_master) ----
-// The gradient value is the bf16 kernel's (load_grad8 / load_grad1, then the clip's bf16(g * coef)); adam_elem then
-// runs on the fp32 master p32 and the fp32 m, v, which are stored as fp32: ATen's fused AdamW on fp32 tensors. The
-// bf16 model parameter is bf16(p32), written and never read. Bytes per element: 14 read (p32, g, m, v) + 14 written
-// (p32, m, v, p), 16 read with an fp32 main_grad. Vector path: 8 elements per lane, two 16-byte accesses per fp32
-// operand and one per bf16 operand (fp32 pointers 32-byte aligned, the rule of grad_vec_ok<true>).
-template <bool GF32, bool CLIP>
-PICO_DEV void adamw_master_chunk(bf16_t* p, float* p32, const void* g, float* m, float* v, int64_t n, int64_t c0,
-                                 const AdamHyper& h, float coef) {
-  const int64_t end = min(n, c0 + CHUNK);
-  const bool vec = (((uintptr_t)p & 15) == 0) && ((((uintptr_t)p32 | (uintptr_t)m | (uintptr_t)v) & 31) == 0) &&
-                   grad_vec_ok<GF32>(g, n);
-  if (vec) {
-    for (int64_t i = c0 + 8 * (int64_t)threadIdx.x; i < end; i += 8 * 256) {
-      f32x4 pw[2], mw[2], vw[2];
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        pw[k] = reinterpret_cast<const f32x4*>(p32 + i)[k];
-        mw[k] = reinterpret_cast<const f32x4*>(m + i)[k];
-        vw[k] = reinterpret_cast<const f32x4*>(v + i)[k];
-      }
-      float gf[8];
-      load_grad8<GF32>(g, i, gf);
-      u16x8 pv;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float pf = pw[j / 4][j % 4], mf = mw[j / 4][j % 4], vf = vw[j / 4][j % 4];
-        if constexpr (CLIP) gf[j] = bf2f(f2bf(gf[j] * coef));
-        adam_elem(pf, gf[j], mf, vf, h);
-        pw[j / 4][j % 4] = pf;
-        mw[j / 4][j % 4] = mf;
-        vw[j / 4][j % 4] = vf;
-        pv[j] = f2bf(pf);
-      }
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        reinterpret_cast<f32x4*>(p32 + i)[k] = pw[k];
-        reinterpret_cast<f32x4*>(m + i)[k] = mw[k];
-        reinterpret_cast<f32x4*>(v + i)[k] = vw[k];
-      }
-      *reinterpret_cast<u16x8*>(p + i) = pv;
-    }
-  } else {
-    for (int64_t i = c0 + threadIdx.x; i < end; i += 256) {
-      float pf = p32[i], mf = m[i], vf = v[i];
-      float gf = load_grad1<GF32>(g, i);
-      if constexpr (CLIP) gf = bf2f(f2bf(gf * coef));
-      adam_elem(pf, gf, mf, vf, h);
-      p32[i] = pf;
-      m[i] = mf;
-      v[i] = vf;
-      p[i] = f2bf(pf);
-    }
-  }
+// The checks every step entry point opens with, then the host-side hyper-parameters: the bias corrections on the
+// host in double, as ATen's fused AdamW takes them (then fp32 in the kernel). sr: the step is also a word of the
+// generator's counter.
+int adamw_prepare(const char* fn, bool sr, int64_t n_chunks, int64_t step, double lr, double beta1, double beta2,
+                  double eps, double weight_decay, AdamHyper* h) {
+  PICO_REQUIRE(n_chunks >= 0 && n_chunks < (1ll << 31), "%s: bad chunk count", fn);
+  PICO_REQUIRE(step >= 1, "%s: step must be >= 1", fn);
+  PICO_REQUIRE(!sr || step < (1ll << 32), "%s: step must be < 2^32 (the generator's counter word)", fn);
+  PICO_REQUIRE(lr >= 0.0 && eps >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+               "%s: invalid hyper-parameters", fn);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  h->lr_wd = (double)lr * (double)weight_decay;
+  h->b1 = beta1;
+  h->b2 = beta2;
+  h->eps = eps;
+  h->bc2_sqrt = sqrt(bc2);
+  h->step_size = (float)((double)lr / bc1);
+  return 0;
 }
 
-template <bool CLIP>
-PICO_DEV void adamw_master_block(const int64_t* tensors, const int64_t* masters, const int64_t* sizes,
-                                 const int64_t* chunks, const AdamHyper& h, float coef) {
-  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
-  const int64_t* t = tensors + 5 * ti;
-  bf16_t* p = (bf16_t*)t[0];
-  float* p32 = (float*)masters[ti];
-  const void* g = (const void*)t[1];
-  float* m = (float*)t[2];
-  float* v = (float*)t[3];
-  if (t[4]) adamw_master_chunk<true, CLIP>(p, p32, g, m, v, sizes[ti], c0, h, coef);
-  else adamw_master_chunk<false, CLIP>(p, p32, g, m, v, sizes[ti], c0, h, coef);
-}
-
-__global__ __launch_bounds__(256) void adamw_master_kernel(const int64_t* __restrict__ tensors,
-                                                           const int64_t* __restrict__ masters,
-                                                           const int64_t* __restrict__ sizes,
-                                                           const int64_t* __restrict__ chunks, AdamHyper h) {
-  adamw_master_block<false>(tensors, masters, sizes, chunks, h, 1.0f);
-}
-
-// norm_coef as in adamw_bf16_clip_kernel: a non-finite norm writes nothing (master, moments, parameter).
-__global__ __launch_bounds__(256) void adamw_master_clip_kernel(const int64_t* __restrict__ tensors,
-                                                                const int64_t* __restrict__ masters,
-                                                                const int64_t* __restrict__ sizes,
-                                                                const int64_t* __restrict__ chunks, AdamHyper h,
-                                                                const float* __restrict__ norm_coef) {
-  const float norm = norm_coef[0], coef = norm_coef[1];
-  if (!isfinite(norm)) return;
-  adamw_master_block<true>(tensors, masters, sizes, chunks, h, coef);
+// One launch of a form, with the clip when norm_coef is not null. Timed under PICO_K_ADAMW.
+template <int FORM>
+int adamw_launch(const char* op, const char* op_clip, const int64_t* tensors, const int64_t* sixth,
+                 const int64_t* sizes, const int64_t* chunks, int64_t n_chunks, const AdamHyper& h, const SrKey& sr,
+                 const float* norm_coef, void* stream) {
+  return pico_launch(PICO_K_ADAMW, norm_coef ? op_clip : op,
+                     norm_coef ? adamw_kernel<FORM, true> : adamw_kernel<FORM, false>, dim3((int)n_chunks), dim3(256), 0,
+                     (hipStream_t)stream, tensors, sixth, sizes, chunks, h, sr, norm_coef);
 }
 
 }  // namespace
@@ -269,119 +291,54 @@ extern "C" int64_t pico_adamw_chunk_elems(void) { return CHUNK; }
 extern "C" int pico_adamw_bf16(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks, int64_t n_chunks,
                                double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                                void* stream) {
-  PICO_REQUIRE(n_chunks >= 0 && n_chunks < (1ll << 31), "pico_adamw_bf16: bad chunk count");
-  PICO_REQUIRE(step >= 1, "pico_adamw_bf16: step must be >= 1");
-  PICO_REQUIRE(lr >= 0.0 && eps >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
-               "pico_adamw_bf16: invalid hyper-parameters");
+  AdamHyper h;
+  PICO_TRY(adamw_prepare("pico_adamw_bf16", false, n_chunks, step, lr, beta1, beta2, eps, weight_decay, &h));
   if (n_chunks == 0) return 0;
   PICO_REQUIRE(tensors && sizes && chunks, "pico_adamw_bf16: null table");
-  // bias corrections on the host in double, as ATen's fused AdamW takes them (then fp32 in the kernel)
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  AdamHyper h;
-  h.lr_wd = (double)lr * (double)weight_decay;
-  h.b1 = beta1;
-  h.b2 = beta2;
-  h.eps = eps;
-  h.bc2_sqrt = sqrt(bc2);
-  h.step_size = (float)((double)lr / bc1);
-  hipStream_t s = (hipStream_t)stream;
-  PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw", adamw_bf16_kernel, dim3((int)n_chunks), dim3(256), 0, s, tensors, sizes, chunks, h));
-  return 0;
+  return adamw_launch<FORM_BF16>("adamw", "adamw_clip", tensors, nullptr, sizes, chunks, n_chunks, h, SrKey{}, nullptr,
+                                 stream);
 }
 
-// pico_adamw_bf16 with the gradient clip folded in: the same checks and host-side hyper-parameters, plus the
-// device (norm, coefficient) pair. Timed under PICO_K_ADAMW.
+// pico_adamw_bf16 with the gradient clip folded in: plus the device (norm, coefficient) pair.
 extern "C" int pico_adamw_bf16_clip(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks,
                                     int64_t n_chunks, double lr, double beta1, double beta2, double eps,
                                     double weight_decay, int64_t step, const float* norm_coef, void* stream) {
-  PICO_REQUIRE(n_chunks >= 0 && n_chunks < (1ll << 31), "pico_adamw_bf16_clip: bad chunk count");
-  PICO_REQUIRE(step >= 1, "pico_adamw_bf16_clip: step must be >= 1");
-  PICO_REQUIRE(lr >= 0.0 && eps >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
-               "pico_adamw_bf16_clip: invalid hyper-parameters");
+  AdamHyper h;
+  PICO_TRY(adamw_prepare("pico_adamw_bf16_clip", false, n_chunks, step, lr, beta1, beta2, eps, weight_decay, &h));
   PICO_REQUIRE(norm_coef, "pico_adamw_bf16_clip: null norm_coef");
   if (n_chunks == 0) return 0;
   PICO_REQUIRE(tensors && sizes && chunks, "pico_adamw_bf16_clip: null table");
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  AdamHyper h;
-  h.lr_wd = (double)lr * (double)weight_decay;
-  h.b1 = beta1;
-  h.b2 = beta2;
-  h.eps = eps;
-  h.bc2_sqrt = sqrt(bc2);
-  h.step_size = (float)((double)lr / bc1);
-  hipStream_t s = (hipStream_t)stream;
-  PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_clip", adamw_bf16_clip_kernel, dim3((int)n_chunks), dim3(256), 0, s, tensors,
-                       sizes, chunks, h, norm_coef));
-  return 0;
+  return adamw_launch<FORM_BF16>("adamw", "adamw_clip", tensors, nullptr, sizes, chunks, n_chunks, h, SrKey{},
+                                 norm_coef, stream);
 }
 
-// The step on fp32 master weights and fp32 moments: pico_adamw_bf16_clip's checks and host-side hyper-parameters,
-// plus the masters table; norm_coef NULL: no clip. Timed under PICO_K_ADAMW.
+// The step on fp32 master weights and fp32 moments: plus the masters table; norm_coef NULL: no clip.
 extern "C" int pico_adamw_master(const int64_t* tensors, const int64_t* masters, const int64_t* sizes,
                                  const int64_t* chunks, int64_t n_chunks, double lr, double beta1, double beta2,
                                  double eps, double weight_decay, int64_t step, const float* norm_coef, void* stream) {
-  PICO_REQUIRE(n_chunks >= 0 && n_chunks < (1ll << 31), "pico_adamw_master: bad chunk count");
-  PICO_REQUIRE(step >= 1, "pico_adamw_master: step must be >= 1");
-  PICO_REQUIRE(lr >= 0.0 && eps >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
-               "pico_adamw_master: invalid hyper-parameters");
+  AdamHyper h;
+  PICO_TRY(adamw_prepare("pico_adamw_master", false, n_chunks, step, lr, beta1, beta2, eps, weight_decay, &h));
   if (n_chunks == 0) return 0;
   PICO_REQUIRE(tensors && sizes && chunks, "pico_adamw_master: null table");
   PICO_REQUIRE(masters, "pico_adamw_master: null masters table");
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  AdamHyper h;
-  h.lr_wd = (double)lr * (double)weight_decay;
-  h.b1 = beta1;
-  h.b2 = beta2;
-  h.eps = eps;
-  h.bc2_sqrt = sqrt(bc2);
-  h.step_size = (float)((double)lr / bc1);
-  hipStream_t s = (hipStream_t)stream;
-  if (norm_coef) {
-    PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_master_clip", adamw_master_clip_kernel, dim3((int)n_chunks), dim3(256), 0,
-                         s, tensors, masters, sizes, chunks, h, norm_coef));
-  } else {
-    PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_master", adamw_master_kernel, dim3((int)n_chunks), dim3(256), 0, s,
-                         tensors, masters, sizes, chunks, h));
-  }
-  return 0;
+  return adamw_launch<FORM_MASTER>("adamw_master", "adamw_master_clip", tensors, masters, sizes, chunks, n_chunks, h,
+                                   SrKey{}, norm_coef, stream);
 }
 
-// The bf16 step with stochastic rounding of the parameter and both moments: pico_adamw_bf16_clip's checks and
-// host-side hyper-parameters, plus the ids table and the seed; norm_coef NULL: no clip. Timed under PICO_K_ADAMW.
+// The bf16 step with stochastic rounding of the parameter and both moments: plus the ids table and the seed;
+// norm_coef NULL: no clip.
 extern "C" int pico_adamw_bf16_sr(const int64_t* tensors, const int64_t* ids, const int64_t* sizes,
                                   const int64_t* chunks, int64_t n_chunks, double lr, double beta1, double beta2,
                                   double eps, double weight_decay, int64_t step, const float* norm_coef, uint64_t seed,
                                   void* stream) {
-  PICO_REQUIRE(n_chunks >= 0 && n_chunks < (1ll << 31), "pico_adamw_bf16_sr: bad chunk count");
-  PICO_REQUIRE(step >= 1, "pico_adamw_bf16_sr: step must be >= 1");
-  PICO_REQUIRE(step < (1ll << 32), "pico_adamw_bf16_sr: step must be < 2^32 (the generator's counter word)");
-  PICO_REQUIRE(lr >= 0.0 && eps >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
-               "pico_adamw_bf16_sr: invalid hyper-parameters");
+  AdamHyper h;
+  PICO_TRY(adamw_prepare("pico_adamw_bf16_sr", true, n_chunks, step, lr, beta1, beta2, eps, weight_decay, &h));
   if (n_chunks == 0) return 0;
   PICO_REQUIRE(tensors && sizes && chunks, "pico_adamw_bf16_sr: null table");
   PICO_REQUIRE(ids, "pico_adamw_bf16_sr: null ids table");
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  AdamHyper h;
-  h.lr_wd = (double)lr * (double)weight_decay;
-  h.b1 = beta1;
-  h.b2 = beta2;
-  h.eps = eps;
-  h.bc2_sqrt = sqrt(bc2);
-  h.step_size = (float)((double)lr / bc1);
   const SrKey sr{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step};
-  hipStream_t s = (hipStream_t)stream;
-  if (norm_coef) {
-    PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_sr_clip", adamw_bf16_sr_kernel<true>, dim3((int)n_chunks), dim3(256), 0,
-                         s, tensors, ids, sizes, chunks, h, sr, norm_coef));
-  } else {
-    PICO_TRY(pico_launch(PICO_K_ADAMW, "adamw_sr", adamw_bf16_sr_kernel<false>, dim3((int)n_chunks), dim3(256), 0, s,
-                         tensors, ids, sizes, chunks, h, sr, norm_coef));
-  }
-  return 0;
+  return adamw_launch<FORM_SR>("adamw_sr", "adamw_sr_clip", tensors, ids, sizes, chunks, n_chunks, h, sr, norm_coef,
+                               stream);
 }
 
 extern "C" int pico_sr_round_bf16(const float* src, void* dst, int64_t n, uint64_t seed, int64_t step, int64_t id,

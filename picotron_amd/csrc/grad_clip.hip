@@ -58,15 +58,10 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const int64_t* __restr
                                                           const int64_t* __restrict__ sizes,
                                                           const int64_t* __restrict__ chunks,
                                                           float* __restrict__ partial) {
-  __shared__ float wave_part[4];
-  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
-  const int64_t* t = tensors + 5 * ti;
-  const void* g = (const void*)t[1];
-  float s = t[4] ? sqnorm_chunk<true>(g, sizes[ti], c0) : sqnorm_chunk<false>(g, sizes[ti], c0);
-  s = wave_sum_dpp(s);
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+  const OptChunk c = opt_chunk(tensors, sizes, chunks);
+  const void* g = (const void*)c.t[1];
+  const float s = c.t[4] ? sqnorm_chunk<true>(g, c.n, c.c0) : sqnorm_chunk<false>(g, c.n, c.c0);
+  block_sum_store(s, partial + blockIdx.x);
 }
 
 // One workgroup: lane t adds partials t, t + 256, ... in double, then a fixed LDS tree over the 256 lanes.
@@ -135,11 +130,10 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const int64_t* __restri
                                                          const float* __restrict__ norm_coef) {
   const float norm = norm_coef[0], coef = norm_coef[1];
   if (!isfinite(norm) || coef == 1.0f) return;
-  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
-  const int64_t* t = tensors + 5 * ti;
-  void* g = (void*)t[1];
-  if (t[4]) scale_chunk<true>(g, sizes[ti], c0, coef);
-  else scale_chunk<false>(g, sizes[ti], c0, coef);
+  const OptChunk c = opt_chunk(tensors, sizes, chunks);
+  void* g = (void*)c.t[1];
+  if (c.t[4]) scale_chunk<true>(g, c.n, c.c0, coef);
+  else scale_chunk<false>(g, c.n, c.c0, coef);
 }
 
 }  // namespace

@@ -77,17 +77,12 @@ __global__ __launch_bounds__(256) void muon_momentum_kernel(const int64_t* __res
                                                             const int64_t* __restrict__ sizes,
                                                             const int64_t* __restrict__ chunks, MuonMom h,
                                                             float* __restrict__ partial) {
-  __shared__ float wave_part[4];
-  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
-  const int64_t* t = tensors + 5 * ti;
-  const void* g = (const void*)t[1];
-  bf16_t* m = (bf16_t*)t[2];
-  bf16_t* u = (bf16_t*)t[3];
-  float s = t[4] ? momentum_chunk<true>(g, m, u, sizes[ti], c0, h) : momentum_chunk<false>(g, m, u, sizes[ti], c0, h);
-  s = wave_sum_dpp(s);
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+  const OptChunk c = opt_chunk(tensors, sizes, chunks);
+  const void* g = (const void*)c.t[1];
+  bf16_t* m = (bf16_t*)c.t[2];
+  bf16_t* u = (bf16_t*)c.t[3];
+  const float s = c.t[4] ? momentum_chunk<true>(g, m, u, c.n, c.c0, h) : momentum_chunk<false>(g, m, u, c.n, c.c0, h);
+  block_sum_store(s, partial + blockIdx.x);
 }
 
 // One workgroup per tensor: its chunk partials go through LDS 256 at a time (coalesced loads) and lane 0 adds them
@@ -129,8 +124,8 @@ __global__ __launch_bounds__(256) void muon_normalize_kernel(const int64_t* __re
                                                              const int64_t* __restrict__ sizes,
                                                              const int64_t* __restrict__ chunks,
                                                              const float* __restrict__ norms) {
-  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
-  normalize_chunk((bf16_t*)tensors[5 * ti + 3], sizes[ti], c0, norms[ti]);
+  const OptChunk c = opt_chunk(tensors, sizes, chunks);
+  normalize_chunk((bf16_t*)c.t[3], c.n, c.c0, norms[c.ti]);
 }
 
 PICO_DEV unsigned short update_elem(unsigned short p, unsigned short o, float decay, float alpha) {
@@ -160,9 +155,9 @@ __global__ __launch_bounds__(256) void muon_update_kernel(const int64_t* __restr
                                                           const int64_t* __restrict__ sizes,
                                                           const int64_t* __restrict__ chunks, double lr, float decay,
                                                           const double* __restrict__ ratios) {
-  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
-  const float alpha = (float)(-(lr * ratios[ti]));
-  update_chunk((bf16_t*)tensors[5 * ti], (const bf16_t*)out_ptrs[ti], sizes[ti], c0, decay, alpha);
+  const OptChunk c = opt_chunk(tensors, sizes, chunks);
+  const float alpha = (float)(-(lr * ratios[c.ti]));
+  update_chunk((bf16_t*)c.t[0], (const bf16_t*)out_ptrs[c.ti], c.n, c.c0, decay, alpha);
 }
 
 }  // namespace

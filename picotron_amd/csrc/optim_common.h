@@ -1,14 +1,37 @@
-// Shared by the whole-parameter-list kernels (adamw.hip, grad_clip.hip): the chunk size of their device
-// tables and the gradient load.
+// Shared by the whole-parameter-list kernels (adamw.hip, grad_clip.hip, muon.hip): their device tables and
+// a workgroup's row of them, the gradient load, the workgroup sum and the stochastic rounding.
 //
-// tensors: [n_tensors][5] = (param, grad, exp_avg, exp_avg_sq pointers, grad_is_f32) as int64; sizes:
-// [n_tensors] numel; chunks: [n_chunks][2] (tensor index, first element).
+// tensors: [n_tensors][5] = (param, grad, exp_avg, exp_avg_sq pointers, grad_is_f32) as int64 (muon.hip: param,
+// grad, momentum_buffer, work, grad_is_f32); sizes: [n_tensors] numel; chunks: [n_chunks][2] (tensor index, first
+// element).
 #pragma once
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 constexpr int OPT_CHUNK = 65536;  // elements per workgroup
+
+// The chunk of workgroup blockIdx.x: tensor index, first element, the tensor's row of `tensors` and its numel.
+struct OptChunk {
+  int64_t ti, c0;
+  const int64_t* t;
+  int64_t n;
+};
+
+PICO_DEV OptChunk opt_chunk(const int64_t* tensors, const int64_t* sizes, const int64_t* chunks) {
+  const int64_t ti = chunks[2 * blockIdx.x], c0 = chunks[2 * blockIdx.x + 1];
+  return {ti, c0, tensors + 5 * ti, sizes[ti]};
+}
+
+// *out = the sum of s over a workgroup of 256 lanes (all of them call), in the fixed order that pico_grad_sqnorm
+// documents (grad_clip.hip): wave_sum_dpp over the 64 lanes, then the four waves' sums pairwise through LDS.
+PICO_DEV void block_sum_store(float s, float* out) {
+  __shared__ float wave_part[4];
+  s = wave_sum_dpp(s);
+  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
 
 // grad_is_f32 = 1: the gradient is DataParallelBucket's averaged fp32 main_grad (its bf16 .grad cast
 // deferred, ref picotron/data_parallel/data_parallel.py:165): each element is rounded to bf16 in register

@@ -391,38 +391,44 @@ class AdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
-        if self.max_grad_norm is not None:
-            self._step_clipped(lib)
+        if self.max_grad_norm is None:  # group by group, each table set on its own stream
+            for gi, group in enumerate(self.param_groups):
+                for step, ps in self._advance(group):
+                    self._launch(lib, self._group_tables(gi, ps), group, step, None, _lib.stream_of(ps[0]))
             return loss
+        # with max_grad_norm: every (group, step count) table set first, one global norm over all of them, then
+        # one launch per set with the same device (norm, coefficient) pair, all on the first set's stream
+        work = []
         for gi, group in enumerate(self.param_groups):
-            beta1, beta2 = group["betas"]
             for step, ps in self._advance(group):
-                ent = self._group_tables(gi, ps)
-                if self.master_weights:
-                    self._launch_master(lib, ent, group, step, None, _lib.stream_of(ps[0]))
-                    continue
-                if self.stochastic_rounding:
-                    self._launch_sr(lib, ent, group, step, None, _lib.stream_of(ps[0]))
-                    continue
-                _lib.check(lib.pico_adamw_bf16(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
-                                               ent["n_chunks"], float(group["lr"]), float(beta1), float(beta2),
-                                               float(group["eps"]), float(group["weight_decay"]), step,
-                                               _lib.stream_of(ps[0])), "pico_adamw_bf16")
+                work.append((group, step, ps, self._group_tables(gi, ps)))
+        if not work:
+            return loss
+        stream = _lib.stream_of(work[0][2][0])
+        groups, tp_rank, tp_world = _norm_groups(self.grad_norm_groups)
+        sums = [_sqnorm(lib, ent, select_norm_params(ps, tp_rank, tp_world), stream) for _, _, ps, ent in work]
+        nc = _norm_coef(lib, sums, groups, self.max_grad_norm, stream)
+        for group, step, _, ent in work:
+            self._launch(lib, ent, group, step, nc, stream)
+        self.grad_norm = nc[0]
         return loss
 
-    def _launch_master(self, lib, ent, group, step, norm_coef, stream):
+    def _launch(self, lib, ent, group, step, norm_coef, stream):
+        """One launch over a table set: the master, stochastic-rounding or plain bf16 step, with the clip folded in
+        when norm_coef (the device (norm, coefficient) pair) is given."""
+        nc = _lib.ptr(norm_coef)
+        if self.master_weights:
+            fn, sixth, tail = lib.pico_adamw_master, (_lib.ptr(ent["masters"]),), (nc, stream)
+        elif self.stochastic_rounding:
+            fn, sixth, tail = lib.pico_adamw_bf16_sr, (_lib.ptr(ent["ids"]),), (nc, self.sr_seed, stream)
+        elif norm_coef is not None:
+            fn, sixth, tail = lib.pico_adamw_bf16_clip, (), (nc, stream)
+        else:
+            fn, sixth, tail = lib.pico_adamw_bf16, (), (stream,)
         beta1, beta2 = group["betas"]
-        _lib.check(lib.pico_adamw_master(_lib.ptr(ent["tens"]), _lib.ptr(ent["masters"]), _lib.ptr(ent["sizes"]),
-                                         _lib.ptr(ent["chunks"]), ent["n_chunks"], float(group["lr"]), float(beta1),
-                                         float(beta2), float(group["eps"]), float(group["weight_decay"]), step,
-                                         _lib.ptr(norm_coef), stream), "pico_adamw_master")
-
-    def _launch_sr(self, lib, ent, group, step, norm_coef, stream):
-        beta1, beta2 = group["betas"]
-        _lib.check(lib.pico_adamw_bf16_sr(_lib.ptr(ent["tens"]), _lib.ptr(ent["ids"]), _lib.ptr(ent["sizes"]),
-                                          _lib.ptr(ent["chunks"]), ent["n_chunks"], float(group["lr"]), float(beta1),
-                                          float(beta2), float(group["eps"]), float(group["weight_decay"]), step,
-                                          _lib.ptr(norm_coef), self.sr_seed, stream), "pico_adamw_bf16_sr")
+        _lib.check(fn(_lib.ptr(ent["tens"]), *sixth, _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]), ent["n_chunks"],
+                      float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
+                      step, *tail), fn.__name__)
 
     def state_dict(self):
         """torch.optim.Optimizer.state_dict; with stochastic_rounding=True it also carries "sr_seed" at the top
@@ -470,33 +476,6 @@ class AdamW(torch.optim.Optimizer):
                 if isinstance(v, torch.Tensor) and v.is_floating_point():
                     t = v.detach().to(device=p.device, dtype=torch.float32)
                     self.state[p][key] = t.clone() if t.data_ptr() == v.data_ptr() else t
-
-    def _step_clipped(self, lib):
-        """The step with max_grad_norm: every (group, step count) table set first, one global norm over all of
-        them, then one pico_adamw_bf16_clip launch per set with the same device (norm, coefficient) pair."""
-        work = []
-        for gi, group in enumerate(self.param_groups):
-            for step, ps in self._advance(group):
-                work.append((group, step, ps, self._group_tables(gi, ps)))
-        if not work:
-            return
-        stream = _lib.stream_of(work[0][2][0])
-        groups, tp_rank, tp_world = _norm_groups(self.grad_norm_groups)
-        sums = [_sqnorm(lib, ent, select_norm_params(ps, tp_rank, tp_world), stream) for _, _, ps, ent in work]
-        nc = _norm_coef(lib, sums, groups, self.max_grad_norm, stream)
-        for group, step, ps, ent in work:
-            if self.master_weights:
-                self._launch_master(lib, ent, group, step, nc, stream)
-                continue
-            if self.stochastic_rounding:
-                self._launch_sr(lib, ent, group, step, nc, stream)
-                continue
-            beta1, beta2 = group["betas"]
-            _lib.check(lib.pico_adamw_bf16_clip(_lib.ptr(ent["tens"]), _lib.ptr(ent["sizes"]), _lib.ptr(ent["chunks"]),
-                                                ent["n_chunks"], float(group["lr"]), float(beta1), float(beta2),
-                                                float(group["eps"]), float(group["weight_decay"]), step,
-                                                _lib.ptr(nc), stream), "pico_adamw_bf16_clip")
-        self.grad_norm = nc[0]
 
 
 # ---- Muon ----
