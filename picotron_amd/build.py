@@ -9,7 +9,6 @@ Usage: python -m picotron_amd.build [--verbose] [--resource-usage]
 import argparse
 import concurrent.futures as cf
 import os
-import re
 import subprocess
 import sys
 
@@ -27,11 +26,15 @@ CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno
 # per-source flags: the split attention backward keeps MFMA results in VGPRs (its softmax reads them every
 # tile; AGPR accumulators cost one v_accvgpr_read per score) and no SLP-packed f32 VALU beside the MFMAs
 # (cdna_hip_programming.md / MI355X_MICROARCH.md: packed f32 ops are an anti-lever there)
+SPLIT_BWD_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]
+# every source with a kernel of the split backward (each includes attn_bwd_split.h); a diagnostic stamp build
+# gives its -D to all of them, so that the workspace tail and the kernels agree (scripts/build_variants.py)
+SPLIT_BWD_SOURCES = ["attn_bwd_split.hip", "attn_bwd_q.hip", "attn_bwd_kv.hip", "attn_bwd_kvp.hip",
+                     "attn_bwd_kvp128.hip"]
 FILE_FLAGS = {
-    "attn_bwd_split.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
+    **{f: SPLIT_BWD_FLAGS for f in SPLIT_BWD_SOURCES},
     "attn_fwd.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
     "attn_fwdp.hip": ["-fno-slp-vectorize", "-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form"],
-    "attn_bwd_split_d128.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 
@@ -40,11 +43,9 @@ def sources():
 
 
 def deps(src):
-    """Files whose change rebuilds `src`: itself, every csrc header, the C-ABI header, this file (per-file
-    flags) and any .hip source it #includes (attn_bwd_split_d128.hip includes attn_bwd_split.hip)."""
+    """Files whose change rebuilds `src`: itself, every csrc header, the C-ABI header and this file (per-file
+    flags). No source #includes another source (tests/test_abi.py holds that)."""
     out = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    with open(src) as f:
-        out += [os.path.join(CSRC, m.group(1)) for m in re.finditer(r'#include "([^"]+\.hip)"', f.read())]
     out.append(os.path.join(HERE, "..", "include", "picotron_hip.h"))
     out.append(os.path.abspath(__file__))
     return out

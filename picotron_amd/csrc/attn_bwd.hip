@@ -5,8 +5,8 @@
 // the (global) O and LSE:  P = exp(scale*QK^T - LSE), dV = P^T dO, dP = dO V^T, delta = rowsum(dO * O),
 // dS = P * (dP - delta), dQ = scale * dS K, dK = scale * dS^T Q.
 //
-// The kernels are the split form for both head dims (attn_bwd_split.hip; attn_bwd_split_d128.hip for D = 128):
-// a query-major dQ kernel and a key-major dK/dV kernel, each output with one owner (no atomics, no dQ slabs).
+// The kernels are the split form for both head dims (attn_bwd_split.hip: plan and launch; attn_bwd_q.hip and
+// attn_bwd_kv*.hip: a query-major dQ kernel and a key-major dK/dV kernel), each output with one owner (no atomics, no dQ slabs).
 // Round 1's fused backward (one kernel per key block, per-key-block fp32 dQ slabs summed by a second pass) was
 // slower at every measured shape and is gone; its kernel ids 8-10 stay reserved in
 // picotron_hip.h so the profiling ids of the others do not move.

@@ -145,7 +145,7 @@ PICO_DEV bf16x8 pack_bf16x8(const float* v) {
 
 PICO_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// ---- shared by the backward kernels (attn_bwd.hip, attn_bwd_split.hip) ----
+// ---- shared by the split backward kernels (attn_bwd_split.h and the attn_bwd_*.hip that include it) ----
 
 // One LDS-DMA piece (16 B per lane, lane-linear at the wave-uniform LDS byte address lds_base) issued
 // from inline asm: the compiler does not see it as an LDS write, so it inserts none of its
@@ -237,47 +237,3 @@ PICO_DEV void rope_bwd8(const pico_attn_args& a, int pos, int i0, float* x1, flo
     x2[j] = w * cf - u * sf;
   }
 }
-
-// dK / dV [b, key, hk, :] = sum over the hsplit workgroups' fp32 partials (fixed order) -> bf16 (strided);
-// dK optionally rotated back (PICO_ATTN_ROPE_BWD). Thread layout as attn_bwd_dq_kernel.
-template <int D>
-__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const pico_attn_args a, const float* __restrict__ dkv_part,
-                                                           int hsplit) {
-  constexpr int TPR = D / 16;
-  const int64_t part = a.batch * a.seqlen_k * a.heads_kv * D;
-  const int64_t rows = a.batch * a.seqlen_k * a.heads_kv;
-  const int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / TPR;
-  const int d0 = (threadIdx.x % TPR) * 8;
-  if (row >= rows) return;
-  const int hk = (int)(row % a.heads_kv);
-  const int64_t bk = row / a.heads_kv;
-  const int key = (int)(bk % a.seqlen_k);
-  const int b = (int)(bk / a.seqlen_k);
-  for (int which = 0; which < 2; ++which) {
-    float x1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, x2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int hs = 0; hs < hsplit; ++hs) {
-      const float* src = dkv_part + (2 * hs + which) * part + row * D + d0;
-      const f32x4 l0 = reinterpret_cast<const f32x4*>(src)[0], l1 = reinterpret_cast<const f32x4*>(src)[1];
-      const f32x4 h0 = reinterpret_cast<const f32x4*>(src + D / 2)[0], h1 = reinterpret_cast<const f32x4*>(src + D / 2)[1];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        x1[j] += l0[j];
-        x1[4 + j] += l1[j];
-        x2[j] += h0[j];
-        x2[4 + j] += h1[j];
-      }
-    }
-    if (which == 0 && (a.flags & PICO_ATTN_ROPE_BWD)) rope_bwd8(a, key, d0, x1, x2);
-    u16x8 o1, o2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      o1[j] = f2bf(x1[j]);
-      o2[j] = f2bf(x2[j]);
-    }
-    bf16_t* dst = which ? (bf16_t*)a.dv + b * a.dv_strides[0] + key * a.dv_strides[1] + hk * a.dv_strides[2]
-                        : (bf16_t*)a.dk + b * a.dk_strides[0] + key * a.dk_strides[1] + hk * a.dk_strides[2];
-    *reinterpret_cast<u16x8*>(dst + d0) = o1;
-    *reinterpret_cast<u16x8*>(dst + d0 + D / 2) = o2;
-  }
-}
-

@@ -1,10 +1,12 @@
-"""Build A/B variants of the HIP library: each variant recompiles ONE source with extra -D flags
+"""Build A/B variants of the HIP library: each variant recompiles one source (or a list) with extra -D flags
 and relinks a full library to picotron_amd/lib/variants/<name>.so (select with PICO_LIB_PATH).
 
-  python scripts/build_variants.py attn_bwd.hip base: unroll:-DPICO_BWD_DQ_UNROLL=1 prev:file=/tmp/old.hip
+  python scripts/build_variants.py attn_fwd.hip base: wgfwd:-DPICO_FWD_WGSTAMP=1 prev:file=/tmp/old.hip
+  python scripts/build_variants.py split_bwd wgkv:-DPICO_BWDKV_WGSTAMP=1 wgq:-DPICO_BWDQ_WGSTAMP=1 kvpstamp:-DPICO_KVP_STAMP=1
 A `file=PATH` token compiles PATH (e.g. an older revision of the source) in place of csrc/<src>. Sources that
-must agree on a define (attn_bwd_split.hip and attn_bwd_split_d128.hip, which #includes it) are given
-together: `attn_bwd_split.hip,attn_bwd_split_d128.hip`.
+must agree on a define are given together, `a.hip,b.hip`; `split_bwd` names every source of the split attention
+backward (build.SPLIT_BWD_SOURCES): a stamp define sizes the workspace tail in attn_bwd_split.hip and writes it in
+the kernel files, so it goes to all of them.
 """
 import os
 import subprocess
@@ -15,7 +17,8 @@ from picotron_amd import build as B  # noqa: E402
 
 
 def main():
-    srcs = sys.argv[1].split(",")  # one source, or several that must share the flags (a.hip,b.hip)
+    # one source, or several that must share the flags (a.hip,b.hip; split_bwd = the split attention backward's)
+    srcs = B.SPLIT_BWD_SOURCES if sys.argv[1] == "split_bwd" else sys.argv[1].split(",")
     B.build()
     out_dir = os.path.join(B.HERE, "lib", "variants")
     os.makedirs(out_dir, exist_ok=True)

@@ -1,7 +1,9 @@
 """Workgroup timeline of attn_bwd_kv_kernel from the PICO_BWDKV_WGSTAMP diagnostic build (C2 causal; PICO_TL_SHAPE=B,S,H,D for another shape):
 per workgroup s_memrealtime (100 MHz) at entry, loop start, loop end, stores drained. Prints the kernel
 span, mean prologue / loop / epilogue per workgroup, the loop share of the summed workgroup time, and the
-mean number of workgroups resident over the span. PICO_LIB_PATH=picotron_amd/lib/variants/wgstamp.so."""
+mean number of workgroups resident over the span. The kernel is csrc/attn_bwd_kv.hip; build with
+`python scripts/build_variants.py split_bwd wgkv:-DPICO_BWDKV_WGSTAMP=1`, run with PICO_ATTN_KVP=0
+PICO_LIB_PATH=picotron_amd/lib/variants/wgkv.so."""
 import ctypes
 import json
 import math

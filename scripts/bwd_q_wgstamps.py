@@ -1,7 +1,9 @@
 """Workgroup timeline of attn_bwd_q_kernel from the PICO_BWDQ_WGSTAMP diagnostic build (C2 causal):
 per workgroup s_memrealtime (100 MHz) at entry, loop start, loop end, stores drained. Prints the kernel
 span, mean prologue / loop / epilogue per workgroup, the loop share of the summed workgroup time, and the
-mean number of workgroups resident over the span. PICO_LIB_PATH=picotron_amd/lib/variants/qstamp.so."""
+mean number of workgroups resident over the span. The kernel is csrc/attn_bwd_q.hip; build with
+`python scripts/build_variants.py split_bwd wgq:-DPICO_BWDQ_WGSTAMP=1`, run with
+PICO_LIB_PATH=picotron_amd/lib/variants/wgq.so."""
 import ctypes
 import json
 import math

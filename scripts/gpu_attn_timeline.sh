@@ -1,6 +1,7 @@
 #!/bin/bash
 # Attention timelines on the box: micro-bench of the shipped kernels, then the workgroup-stamp variants
-# (built beforehand with scripts/build_variants.py: wgkv / wgq / wgfwd).
+# (built beforehand: scripts/build_variants.py split_bwd wgkv:-DPICO_BWDKV_WGSTAMP=1 wgq:-DPICO_BWDQ_WGSTAMP=1
+#  and scripts/build_variants.py attn_fwd.hip wgfwd:-DPICO_FWD_WGSTAMP=1).
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out

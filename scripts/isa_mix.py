@@ -1,7 +1,8 @@
 """Instruction mix per basic block of one kernel in the gfx950 assembly of a csrc/ source (CPU only: hipcc -S):
 
   python scripts/isa_mix.py attn_fwd.hip attn_fwd_kernelILi64ELb1E
-  python scripts/isa_mix.py attn_bwd_split.hip attn_bwd_q_kernelILi64ELb1E
+  python scripts/isa_mix.py attn_bwd_q.hip attn_bwd_q_kernelILi64ELb1E
+  python scripts/isa_mix.py attn_bwd_kvp128.hip attn_bwd_kvp128_kernelILb1E
 
 Prints every block with an MFMA or more than 40 vector instructions: its size, MFMA and VALU counts and the most
 frequent vector / LDS / wait instructions — the tile bodies of an attention loop are the blocks with MFMAs.

@@ -4,6 +4,7 @@ cursor, M1(A) slots, M1(B) slots, M2(A) slots, M2(B) slots — which are ISSUE t
 issues, not when it completes). Prints the mean cycles per 64-row tile and phase, overall and by the workgroup's
 dispatch class (block group g -> g * nbh / CUs: oldest first). The stamps cost ~10 % themselves.
 
+  python scripts/build_variants.py split_bwd kvpstamp:-DPICO_KVP_STAMP=1   (kernels: csrc/attn_bwd_kvp.hip, attn_bwd_kvp128.hip)
   PICO_LIB_PATH=picotron_amd/lib/variants/kvpstamp.so PICO_ATTN_KVP=1 python scripts/kvp_stamps.py
 (PICO_KVP_WAVES=8 for the 8-wave workgroups: the stamps are 16 words per wave at (block * NW + wave) * 16.)
 """

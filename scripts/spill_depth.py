@@ -1,7 +1,7 @@
 """Where a kernel's scratch spills / reloads sit, by loop depth, from hipcc's gfx950 assembly (a reload inside the
 tile loop costs a vmcnt(0) that drains the LDS-DMA ring every tile).
 
-  python scripts/spill_depth.py picotron_amd/csrc/attn_bwd_split.hip [kernel-substring ...]
+  python scripts/spill_depth.py picotron_amd/csrc/attn_bwd_kv.hip [kernel-substring ...]
 """
 import os
 import re

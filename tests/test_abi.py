@@ -93,6 +93,42 @@ def test_workspace_sizes(lib):
     assert lib.pico_attn_bwd_workspace_bytes(ctypes.byref(a)) == 2 * 32 * 16384 * 4
 
 
+def test_workspace_sizes_follow_the_forced_kernel(lib):
+    """The workspace is sized from the same plan as the launch, so a forced dK/dV kernel (pico_select) sizes the
+    fp32 partials for its own block size and workgroups per CU. Expected values: the library before the plan
+    was factored out (one-time record)."""
+    from picotron_amd import _lib
+
+    def ws(shape, kvp=_lib.SEL_AUTO, waves=_lib.SEL_AUTO):
+        a = _lib.AttnArgs()
+        a.batch, a.seqlen_q, a.heads_q, a.heads_kv, a.head_dim, a.causal = shape
+        a.seqlen_k = a.seqlen_q
+        old = _lib.select(_lib.SEL_ATTN_KVP, kvp), _lib.select(_lib.SEL_KVP_WAVES, waves)
+        try:
+            return lib.pico_attn_bwd_workspace_bytes(ctypes.byref(a))
+        finally:
+            _lib.select(_lib.SEL_ATTN_KVP, old[0])
+            _lib.select(_lib.SEL_KVP_WAVES, old[1])
+
+    # D 64 causal, S 2048, GQA 32/8: 16 key blocks x B 4 x 8 kv heads = 512 workgroups. The 32-row kernel (the rule
+    # beyond 1536 keys, or forced) runs three per CU -> tile lists split 2 ways; the 64-row kernel two per CU -> none
+    c64 = (4, 2048, 32, 8, 64, 1)
+    lsd = 2 * 4 * 32 * 2048 * 4
+    assert ws(c64) == ws(c64, kvp=0) == lsd + 2 * 2 * 4 * 2048 * 8 * 64 * 4
+    assert ws(c64, kvp=1) == lsd
+    # D 64 non-causal, S 1152, 28 heads: 9 blocks of 128 keys x 28 = 252 workgroups for 512 slots -> 4 parts;
+    # 8 waves: 5 blocks of 256 keys x 28 = 140 for 256 slots -> 2 parts. The wave knob is the 64-row kernel's only
+    n64 = (1, 1152, 28, 28, 64, 0)
+    lsd, part = 2 * 28 * 1152 * 4, 2 * 1152 * 28 * 64 * 4
+    assert ws(n64) == ws(n64, waves=4) == ws(n64, kvp=0, waves=8) == lsd + 4 * part
+    assert ws(n64, waves=8) == lsd + 2 * part
+    # D 128: both dK/dV kernels run 128-key blocks at one workgroup per CU, so either knob leaves the size alone
+    lsd, part = 2 * 2 * 32 * 1024 * 4, 2 * 2 * 1024 * 8 * 128 * 4
+    for causal in (0, 1):
+        d128 = (2, 1024, 32, 8, 128, causal)
+        assert ws(d128, kvp=0) == ws(d128, kvp=1) == ws(d128, kvp=1, waves=8) == lsd + 2 * part
+
+
 def test_ops_fail_loudly_without_hip_tensors(lib):
     from picotron_amd import ops
     x = torch.randn(2, 8, 2, 64, dtype=torch.bfloat16)
@@ -164,14 +200,25 @@ def test_weight_transpose_cache_host_logic(monkeypatch):
 
 
 def test_build_tracks_included_sources():
-    """A translation unit that #includes another .hip source is rebuilt when that source changes (a stale
-    attn_bwd_split_d128.o once sized its dK/dV partial writes for another split count than the workspace)."""
+    """No stale object when shared code changes (a stale D = 128 object, built from a source that #included
+    attn_bwd_split.hip, once sized its dK/dV partial writes for another split count than the workspace): every
+    split-backward source is rebuilt when the shared kernel header, the plan header or the build flags change,
+    and no source #includes another source, which deps() would not see."""
     import os
     from picotron_amd import build as B
-    d128 = os.path.join(B.CSRC, "attn_bwd_split_d128.hip")
-    deps = B.deps(d128)
-    assert os.path.join(B.CSRC, "attn_bwd_split.hip") in deps
-    assert os.path.abspath(B.__file__) in deps
+    on_disk = {os.path.basename(s) for s in B.sources()}
+    assert set(B.SPLIT_BWD_SOURCES) <= on_disk and len(B.SPLIT_BWD_SOURCES) >= 5
+    for name in on_disk:
+        with open(os.path.join(B.CSRC, name)) as f:
+            text = f.read()
+        assert not re.search(r'#\s*include\s*["<][^">]+\.hip[">]', text), f"{name} includes a .hip source"
+        if '#include "attn_bwd_split.h"' in text:
+            assert name in B.SPLIT_BWD_SOURCES and B.FILE_FLAGS[name] == B.SPLIT_BWD_FLAGS, name
+    for name in B.SPLIT_BWD_SOURCES:
+        deps = [os.path.normpath(d) for d in B.deps(os.path.join(B.CSRC, name))]
+        for shared in ("attn_bwd_split.h", "attn_bwd_plan.h", "attn_common.h"):
+            assert os.path.join(B.CSRC, shared) in deps, (name, shared)
+        assert os.path.abspath(B.__file__) in deps
 
 
 def test_flash_atten_0_is_refused(monkeypatch):

@@ -17,7 +17,19 @@ import pytest
 
 from picotron_amd import build
 
-SOURCES = ["attn_fwd.hip", "attn_bwd_split.hip", "attn_bwd_split_d128.hip"]
+
+
+def _sources():
+    """Every .hip that can reach `dma_piece`: the ones including attn_common.h, directly or through a csrc header."""
+    def text(f):
+        with open(os.path.join(build.CSRC, f)) as fh:
+            return fh.read()
+    names = os.listdir(build.CSRC)
+    via = ["attn_common.h"] + [f for f in names if f.endswith(".h") and '#include "attn_common.h"' in text(f)]
+    return sorted(f for f in names if f.endswith(".hip") and any(f'#include "{h}"' in text(f) for h in via))
+
+
+SOURCES = _sources()
 _DMA = re.compile(r"(global_load_lds_|buffer_load_\w+ .*\blds\b)")
 _M0_WRITE = re.compile(r"^s_\w+\s+m0\b")
 _BRANCH = re.compile(r"^s_(c?branch|setpc|endpgm)")
