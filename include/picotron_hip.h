@@ -23,6 +23,10 @@
  *   pico_scale_f32            <- grad_data /= process_group_size     (ref picotron/data_parallel/bucket.py:30)
  *   pico_cross_entropy_fwd/_bwd <- F.cross_entropy(logits, target, reduction='mean')
  *                                 (ref train.py:46-49, picotron/pipeline_parallel/pipeline_parallel.py:68,98)
+ *   pico_ce_vp_partial / _combine / _grad
+ *                             <- the same loss under tensor parallelism on each rank's vocabulary shard of the
+ *                                 logits, instead of the LM head's all-gather followed by the full-vocabulary loss
+ *                                 (ref picotron/tensor_parallel/tensor_parallel.py:50, gather_output=True)
  *   pico_adamw_bf16           <- torch.optim.AdamW(..., fused=True).step() (ref train.py:204-209,235)
  *   pico_grad_sqnorm / _clip_coef / _scale, pico_adamw_bf16_clip
  *                             <- torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm): no reference call
@@ -404,6 +408,36 @@ int pico_ce_scale_grad(void* dx, int64_t n, const void* upstream, int upstream_f
 int pico_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* target, const float* lse,
                            const float* grad_scale, void* dlogits, int64_t ldd, int64_t rows, int64_t vocab,
                            int64_t ignore_index, void* stream);
+
+/* ---- vocab-parallel softmax cross-entropy (tensor parallelism) ----
+ * Every tp rank holds the columns [vocab_start, vocab_start + vocab_local) of the [rows, vocab_total] logits:
+ * logits is this rank's [rows, vocab_local] bf16 shard, row stride ld (elements); target: [rows] int64 on the
+ * GLOBAL vocabulary. The softmax statistics are split across the shards, so the caller all-gathers three fp32
+ * numbers per row between partial and combine instead of the logits.
+ * All three: vocab_local, vocab_start, ld (and ldd) multiples of 8, ld (ldd) >= vocab_local, vocab_start +
+ * vocab_local <= vocab_total, 16-byte aligned logits / dlogits; rows == 0 returns 0 before the pointers are read.
+ * partial: one read of the shard. part: fp32 [3][rows] — part[0][i] = m_i = max_j x_ij, part[1][i] = s_i =
+ *          sum_j exp(x_ij - m_i), part[2][i] = x_i[t_i - vocab_start] when the target lives on this shard, else 0.
+ *          A shard row of -inf only gives m = -inf, s = 0 (no NaN). ignore_index is accepted for symmetry; the
+ *          skip rule is applied by combine and grad.
+ * combine: parts: fp32 [tp][3][rows], the gathered planes in rank order. M = max_r m_r, S = sum_r s_r exp(m_r - M)
+ *          added in rank order (a term with m_r = -inf counts 0), lse[i] = M + log S, loss[i] = lse[i] - sum_r xt_r,
+ *          and loss[i] = 0 when t == ignore_index || t < 0 || t >= vocab_total (the skip rule of
+ *          pico_cross_entropy_fwd on the global vocabulary). Fixed order: every rank computes the same bits from
+ *          the same planes. The caller sums loss[] and divides by the non-ignored count (pico_ce_count / _mean).
+ * grad:    dlogits[i][j] = (exp(x_ij - lse[i]) - [j + vocab_start == t_i]) * (*grad_scale), row stride ldd;
+ *          grad_scale is a DEVICE fp32 scalar as in pico_cross_entropy_bwd; skipped rows are written as zeros. A row
+ *          whose target lives on another shard still gets its softmax term (which a shifted target passed to
+ *          pico_cross_entropy_bwd would skip). dlogits may be logits itself (in place) when ldd == ld: each lane
+ *          reads its 16-byte chunks before it writes them. */
+int pico_ce_vp_partial(const void* logits, int64_t ld, const int64_t* target, float* part, int64_t rows,
+                       int64_t vocab_local, int64_t vocab_start, int64_t vocab_total, int64_t ignore_index,
+                       void* stream);
+int pico_ce_vp_combine(const float* parts, int64_t tp, const int64_t* target, int64_t rows, int64_t vocab_total,
+                       int64_t ignore_index, float* lse, float* loss, void* stream);
+int pico_ce_vp_grad(const void* logits, int64_t ld, const int64_t* target, const float* lse, const float* grad_scale,
+                    void* dlogits, int64_t ldd, int64_t rows, int64_t vocab_local, int64_t vocab_start,
+                    int64_t vocab_total, int64_t ignore_index, void* stream);
 
 /* ---- 2-D transpose ----
  * dst[c][r] = src[r][c] for a [rows, cols] bf16 matrix with row stride ld_src into [cols, rows] with row

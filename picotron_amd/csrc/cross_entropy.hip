@@ -251,6 +251,191 @@ extern "C" int pico_cross_entropy_bwd(const void* logits, int64_t ld, const int6
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Vocab-parallel cross-entropy (tensor parallelism, Megatron's vocab_parallel_cross_entropy): every tp rank
+// holds a [rows, vocab_local] column shard of the logits and the softmax statistics are split across the
+// shards, so three fp32 numbers per row cross the wire instead of the vocabulary:
+//   partial: one read of the shard -> part[0] = m (row maximum over the shard), part[1] = s = sum exp(x - m),
+//            part[2] = xt (the target's logit when the target lives on this shard, else 0);
+//   (all-gather of the [3, rows] planes over the tp group, by the caller)
+//   combine: M = max_r m_r, S = sum_r s_r exp(m_r - M) in rank order, lse = M + log S, loss = lse - sum_r xt_r:
+//            the same bits on every rank, from the same gathered planes;
+//   grad:    one read of the shard -> dlogits = (exp(x - lse) - [j + vocab_start == t]) * (*gscale), one write
+//            (in place when dlogits == logits: a lane reads its 16-byte chunk before it writes it). A row whose
+//            target lives on another shard still gets its softmax term.
+// Same form as ce_fwd_kernel / ce_bwd_kernel: one 256-thread workgroup per row, the row in registers between
+// the max and the sum passes, exp(x - m) = exp2(fma(x, log2 e, -m log2 e)).
+namespace {
+
+template <int NCH>
+__global__ __launch_bounds__(256) void ce_vp_partial_kernel(const bf16_t* __restrict__ logits, int64_t ld,
+                                                            const int64_t* __restrict__ target,
+                                                            float* __restrict__ part, int64_t rows, int vocab_local,
+                                                            int64_t vocab_start) {
+  __shared__ float red[4];
+  const int64_t row = blockIdx.x;
+  const bf16_t* x = logits + row * ld;
+  const int nchunk = vocab_local / 8;
+  u16x8 v[NCH];
+  float m = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int ch = threadIdx.x + 256 * c;
+    if (ch < nchunk) {
+      v[c] = *reinterpret_cast<const u16x8*>(x + 8 * ch);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) m = fmaxf(m, bf2f(v[c][j]));
+    }
+  }
+  m = block_reduce<256>(m, red, true);
+  float s = 0.f;
+  if (m != -INFINITY) {  // a shard row of -inf only: s = 0 (exp(-inf - -inf) would be NaN); uniform per block
+    const float nm2 = -m * LOG2E;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = threadIdx.x + 256 * c;
+      if (ch < nchunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += __builtin_amdgcn_exp2f(__builtin_fmaf(bf2f(v[c][j]), LOG2E, nm2));
+      }
+    }
+  }
+  s = block_reduce<256>(s, red, false);
+  if (threadIdx.x == 0) {
+    const int64_t tl = target[row] - vocab_start;
+    part[row] = m;
+    part[rows + row] = s;
+    part[2 * rows + row] = (tl >= 0 && tl < vocab_local) ? bf2f(x[tl]) : 0.f;
+  }
+}
+
+// One thread per row over the gathered planes parts[tp][3][rows]; the ranks are visited in order, so every rank
+// computes the same bits. Precise expf / logf: tp terms per row, nothing to save.
+__global__ __launch_bounds__(256) void ce_vp_combine_kernel(const float* __restrict__ parts, int tp,
+                                                            const int64_t* __restrict__ target, int64_t rows,
+                                                            int64_t vocab_total, int64_t ignore,
+                                                            float* __restrict__ lse, float* __restrict__ loss) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= rows) return;
+  float M = -INFINITY;
+  for (int r = 0; r < tp; ++r) M = fmaxf(M, parts[(int64_t)r * 3 * rows + row]);
+  float S = 0.f, xt = 0.f;
+  for (int r = 0; r < tp; ++r) {
+    const float* p = parts + (int64_t)r * 3 * rows + row;
+    const float mr = p[0];
+    if (mr != -INFINITY) S += p[rows] * expf(mr - M);
+    xt += p[2 * rows];
+  }
+  const float l = M + logf(S);
+  const int64_t t = target[row];
+  lse[row] = l;
+  loss[row] = (t == ignore || t < 0 || t >= vocab_total) ? 0.f : l - xt;
+}
+
+// logits / dlogits may be the same buffer: no __restrict__ on them
+template <int NCH>
+__global__ __launch_bounds__(256) void ce_vp_grad_kernel(const bf16_t* logits, int64_t ld,
+                                                         const int64_t* __restrict__ target,
+                                                         const float* __restrict__ lse,
+                                                         const float* __restrict__ gscale, bf16_t* dlogits, int64_t ldd,
+                                                         int vocab_local, int64_t vocab_start, int64_t vocab_total,
+                                                         int64_t ignore) {
+  const int64_t row = blockIdx.x;
+  const bf16_t* x = logits + row * ld;
+  bf16_t* dx = dlogits + row * ldd;
+  const int nchunk = vocab_local / 8;
+  const int64_t t = target[row];
+  if (t == ignore || t < 0 || t >= vocab_total) {  // skipped row: zeros, the logits are not read (uniform per block)
+    const u16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = threadIdx.x + 256 * c;
+      if (ch < nchunk) *reinterpret_cast<u16x8*>(dx + 8 * ch) = z;
+    }
+    return;
+  }
+  const int64_t tl = t - vocab_start;  // outside [0, vocab_local) when the target lives on another shard
+  const float g = *gscale;
+  const float nl2 = -lse[row] * LOG2E;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int ch = threadIdx.x + 256 * c;
+    if (ch < nchunk) {
+      const u16x8 xv = *reinterpret_cast<const u16x8*>(x + 8 * ch);
+      u16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float p = __builtin_amdgcn_exp2f(__builtin_fmaf(bf2f(xv[j]), LOG2E, nl2));
+        if (8 * ch + j == tl) p -= 1.f;
+        o[j] = f2bf(p * g);
+      }
+      *reinterpret_cast<u16x8*>(dx + 8 * ch) = o;
+    }
+  }
+}
+
+// the shard geometry every vocab-parallel entry point checks (op: the entry point's name)
+int ce_vp_check_shard(const char* op, int64_t rows, int64_t vocab_local, int64_t vocab_start, int64_t vocab_total,
+                      int64_t ld) {
+  PICO_REQUIRE(rows >= 0 && rows < (1ll << 31), "%s: bad row count %lld", op, (long long)rows);
+  PICO_REQUIRE(vocab_local > 0 && vocab_local % 8 == 0, "%s: vocab_local (%lld) must be a positive multiple of 8", op,
+               (long long)vocab_local);
+  PICO_REQUIRE(ld % 8 == 0 && ld >= vocab_local, "%s: row stride (%lld) must be a multiple of 8 and >= vocab_local", op,
+               (long long)ld);
+  PICO_REQUIRE(vocab_start >= 0 && vocab_start % 8 == 0, "%s: vocab_start (%lld) must be a non-negative multiple of 8",
+               op, (long long)vocab_start);
+  PICO_REQUIRE(vocab_start + vocab_local <= vocab_total, "%s: shard [%lld, %lld) exceeds vocab_total %lld", op,
+               (long long)vocab_start, (long long)(vocab_start + vocab_local), (long long)vocab_total);
+  PICO_REQUIRE(nch_for(vocab_local) > 0, "%s: vocab_local %lld too large", op, (long long)vocab_local);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int pico_ce_vp_partial(const void* logits, int64_t ld, const int64_t* target, float* part, int64_t rows,
+                                  int64_t vocab_local, int64_t vocab_start, int64_t vocab_total, int64_t ignore_index,
+                                  void* stream) {
+  (void)ignore_index;  // the skip rule is applied on the global vocabulary, in combine and grad
+  PICO_TRY(ce_vp_check_shard("pico_ce_vp_partial", rows, vocab_local, vocab_start, vocab_total, ld));
+  if (rows == 0) return 0;
+  PICO_REQUIRE(logits && target && part, "pico_ce_vp_partial: null pointer");
+  PICO_REQUIRE((uintptr_t)logits % 16 == 0, "pico_ce_vp_partial: logits must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  CE_SWITCH(nch_for(vocab_local), PICO_TRY(pico_launch(PICO_K_CE_FWD, "ce_vp_partial", ce_vp_partial_kernel<N>, dim3((int)rows), dim3(256), 0, s, (const bf16_t*)logits, ld, target, part, rows,
+                                                       (int)vocab_local, vocab_start)))
+  return 0;
+}
+
+extern "C" int pico_ce_vp_combine(const float* parts, int64_t tp, const int64_t* target, int64_t rows,
+                                  int64_t vocab_total, int64_t ignore_index, float* lse, float* loss, void* stream) {
+  PICO_REQUIRE(rows >= 0 && rows < (1ll << 31), "pico_ce_vp_combine: bad row count %lld", (long long)rows);
+  PICO_REQUIRE(tp >= 1 && tp <= 65536, "pico_ce_vp_combine: bad tp size %lld", (long long)tp);
+  PICO_REQUIRE(vocab_total > 0, "pico_ce_vp_combine: bad vocab_total %lld", (long long)vocab_total);
+  if (rows == 0) return 0;
+  PICO_REQUIRE(parts && target && lse && loss, "pico_ce_vp_combine: null pointer");
+  PICO_TRY(pico_launch(PICO_K_CE_FWD, "ce_vp_combine", ce_vp_combine_kernel, dim3(pico_cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, parts, (int)tp, target, rows, vocab_total, ignore_index, lse,
+                       loss));
+  return 0;
+}
+
+extern "C" int pico_ce_vp_grad(const void* logits, int64_t ld, const int64_t* target, const float* lse,
+                               const float* grad_scale, void* dlogits, int64_t ldd, int64_t rows, int64_t vocab_local,
+                               int64_t vocab_start, int64_t vocab_total, int64_t ignore_index, void* stream) {
+  PICO_TRY(ce_vp_check_shard("pico_ce_vp_grad", rows, vocab_local, vocab_start, vocab_total, ld));
+  PICO_REQUIRE(ldd % 8 == 0 && ldd >= vocab_local,
+               "pico_ce_vp_grad: dlogits row stride (%lld) must be a multiple of 8 and >= vocab_local", (long long)ldd);
+  if (rows == 0) return 0;
+  PICO_REQUIRE(logits && target && lse && grad_scale && dlogits, "pico_ce_vp_grad: null pointer");
+  PICO_REQUIRE((uintptr_t)logits % 16 == 0 && (uintptr_t)dlogits % 16 == 0,
+               "pico_ce_vp_grad: logits and dlogits must be 16-byte aligned");
+  PICO_REQUIRE(logits != dlogits || ldd == ld, "pico_ce_vp_grad: in place needs ldd == ld");
+  hipStream_t s = (hipStream_t)stream;
+  CE_SWITCH(nch_for(vocab_local), PICO_TRY(pico_launch(PICO_K_CE_BWD, "ce_vp_grad", ce_vp_grad_kernel<N>, dim3((int)rows), dim3(256), 0, s, (const bf16_t*)logits, ld, target, lse, grad_scale,
+                                                       (bf16_t*)dlogits, ldd, (int)vocab_local, vocab_start,
+                                                       vocab_total, ignore_index)))
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The mean's scalar bookkeeping around the fused LM-head CE (ref train.py:46-49, reduction='mean'), one
 // 1024-thread workgroup each instead of ~9 ATen scalar launches per micro-batch:
 //   pico_ce_count: stats[0] = number of targets != ignore_index, stats[1] = grad_scale / stats[0]

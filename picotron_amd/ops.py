@@ -997,6 +997,95 @@ def cross_entropy(logits, target, ignore_index=-100, reduction="mean"):
     return _CrossEntropyFn.apply(logits, target, ignore_index)
 
 
+# Vocab-parallel cross-entropy (tensor parallelism): launch wrappers of pico_ce_vp_partial / _combine / _grad.
+# The collective between partial and combine and the autograd nodes live in
+# picotron_amd.tensor_parallel.vocab_parallel_loss (which imports this module, not the other way round).
+def _need_targets(t, rows):
+    _need(t, "target", torch.int64)
+    if t.dim() != 1 or t.shape[0] != rows or not t.is_contiguous():
+        raise ValueError(f"target must be a contiguous [{rows}] int64 tensor, got {tuple(t.shape)}")
+
+
+def _need_shard(logits, name="logits"):
+    _need(logits, name)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError(f"{name} must be [rows, vocab_local] with unit column stride")
+
+
+def ce_vp_partial(logits, target, vocab_start, vocab_total, ignore_index=-100):
+    """This rank's softmax statistics of a [rows, vocab_local] bf16 logits shard (a column slice is fine):
+    fp32 [3, rows] = (row max, sum exp(x - max), the target's logit if it lives on this shard else 0)."""
+    _need_shard(logits)
+    rows, vl = logits.shape
+    _need_targets(target, rows)
+    part = torch.empty(3, rows, dtype=torch.float32, device=logits.device)
+    _lib.check(_lib.load().pico_ce_vp_partial(_lib.ptr(logits), logits.stride(0), _lib.ptr(target), _lib.ptr(part),
+                                              rows, vl, int(vocab_start), int(vocab_total), int(ignore_index),
+                                              _lib.stream_of(logits)), "pico_ce_vp_partial")
+    return part
+
+
+def ce_vp_combine(parts, target, vocab_total, ignore_index=-100):
+    """(lse, loss_rows), fp32 [rows] each, from the gathered planes parts [tp, 3, rows] (rank order): the same
+    bits on every rank."""
+    _need(parts, "parts", torch.float32)
+    if parts.dim() != 3 or parts.shape[1] != 3 or not parts.is_contiguous():
+        raise ValueError(f"parts must be a contiguous [tp, 3, rows] tensor, got {tuple(parts.shape)}")
+    tp, _, rows = parts.shape
+    _need_targets(target, rows)
+    lse = torch.empty(rows, dtype=torch.float32, device=parts.device)
+    loss_rows = torch.empty(rows, dtype=torch.float32, device=parts.device)
+    _lib.check(_lib.load().pico_ce_vp_combine(_lib.ptr(parts), tp, _lib.ptr(target), rows, int(vocab_total),
+                                              int(ignore_index), _lib.ptr(lse), _lib.ptr(loss_rows),
+                                              _lib.stream_of(parts)), "pico_ce_vp_combine")
+    return lse, loss_rows
+
+
+def ce_vp_grad(logits, target, lse, grad_scale, vocab_start, vocab_total, ignore_index=-100, out=None):
+    """dlogits of this rank's shard = (exp(x - lse) - onehot(target - vocab_start)) * grad_scale (fp32 device
+    scalar; zeros for skipped rows). out=None: a fresh contiguous [rows, vocab_local] tensor; out=logits: in place."""
+    _need_shard(logits)
+    rows, vl = logits.shape
+    _need_targets(target, rows)
+    _need(lse, "lse", torch.float32)
+    _need(grad_scale, "grad_scale", torch.float32)
+    if lse.shape != (rows,) or not lse.is_contiguous() or grad_scale.numel() != 1:
+        raise ValueError("lse must be a contiguous [rows] tensor and grad_scale a single element")
+    if out is None:
+        out = torch.empty(rows, vl, dtype=logits.dtype, device=logits.device)
+    else:
+        _need_shard(out, "out")
+        if out.shape != logits.shape:
+            raise ValueError(f"out must have the logits' shape {tuple(logits.shape)}, got {tuple(out.shape)}")
+    _lib.check(_lib.load().pico_ce_vp_grad(_lib.ptr(logits), logits.stride(0), _lib.ptr(target), _lib.ptr(lse),
+                                           _lib.ptr(grad_scale), _lib.ptr(out), out.stride(0), rows, vl,
+                                           int(vocab_start), int(vocab_total), int(ignore_index),
+                                           _lib.stream_of(logits)), "pico_ce_vp_grad")
+    return out
+
+
+def ce_count(target, ignore_index=-100, grad_scale=1.0):
+    """fp32 [2] = (number of targets != ignore_index, grad_scale / that count), one launch (pico_ce_count)."""
+    _need(target, "target", torch.int64)
+    stats = torch.empty(2, dtype=torch.float32, device=target.device)
+    _lib.check(_lib.load().pico_ce_count(_lib.ptr(target), target.numel(), int(ignore_index), float(grad_scale),
+                                         _lib.ptr(stats), _lib.stream_of(target)), "pico_ce_count")
+    return stats
+
+
+def ce_mean(loss_rows, stats, dtype, grad_scale=1.0):
+    """0-dim `dtype` (bf16 or fp32) tensor = grad_scale * sum(loss_rows) / stats[0], summed in a fixed order
+    (pico_ce_mean)."""
+    _need(loss_rows, "loss_rows", torch.float32)
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"ce_mean: bf16 or fp32 output, got {dtype}")
+    loss = torch.empty((), dtype=dtype, device=loss_rows.device)
+    _lib.check(_lib.load().pico_ce_mean(_lib.ptr(loss_rows), loss_rows.numel(), _lib.ptr(stats), float(grad_scale),
+                                        _lib.ptr(loss), 1 if dtype == torch.float32 else 0, None,
+                                        _lib.stream_of(loss_rows)), "pico_ce_mean")
+    return loss
+
+
 def embedding(ids, w):
     if not wgrad_fusion_enabled():
         return torch.nn.functional.embedding(ids, w)

@@ -29,8 +29,14 @@ from .tp_communications import (GatherFromModelParallelRegion, ReduceFromModelPa
                                 linear_with_async_all_reduce)
 
 
-def apply_tensor_parallel(model, shard_weights=False):
-    """ref :9-51. shard_weights: take each rank's shard of the existing weights instead of re-initialising."""
+def apply_tensor_parallel(model, shard_weights=False, vocab_parallel_loss=False):
+    """ref :9-51. shard_weights: take each rank's shard of the existing weights instead of re-initialising.
+    vocab_parallel_loss: build the LM head without the all-gather of its output (gather_output=False) and mark it
+    (final_proj.vocab_parallel_loss = True): model(input_ids) then returns this rank's [B, S, V/tp] logits instead
+    of the gathered [B, S, V], to be reduced by vocab_parallel_loss.vocab_parallel_cross_entropy (or take
+    model(..., return_hidden=True), which is unchanged, and vocab_parallel_lm_head_cross_entropy on final_proj.weight:
+    the LM head fused with the loss). The full logits never exist on any rank. train.train_step does not look at
+    the mark (it would read the local logits as the whole vocabulary): with this switch the loss is the caller's."""
     m = pgm.process_group_manager
 
     def _replace_module(_module, _linear_proj_name, _style, args={}):
@@ -73,7 +79,9 @@ def apply_tensor_parallel(model, shard_weights=False):
         for module_name, proj, style in mapping:
             _replace_module(getattr(layer, module_name), proj, style)
     _replace_module(model, "embedding", "vocab")
-    _replace_module(model, "final_proj", "column", args={"gather_output": True})
+    _replace_module(model, "final_proj", "column", args={"gather_output": not vocab_parallel_loss})
+    if vocab_parallel_loss:
+        model.final_proj.vocab_parallel_loss = True
     return model
 
 
