@@ -1238,6 +1238,80 @@ def _check_qkv(q, k, v):
         raise ValueError("flash attention: heads_q must be a multiple of heads_kv")
 
 
+# Packed rows: several documents share one row of the batch. doc_start[b, i] is the index of the first token of the
+# document that holds token i (non-decreasing along the row, doc_start[b, 0] == 0, doc_start[b, i] <= i); under a
+# document mask query i sees key j iff doc_start[b, i] <= j <= i. The helpers below are plain torch and work on any
+# device; they describe the mask, no kernel here applies it yet.
+def doc_starts_from_eos(input_ids, eos_token_id):
+    """doc_start int32 [B, S] of packed rows: a token that follows an EOS opens a new document, and token 0
+    always does (the EOS itself is the last token of its document)."""
+    if input_ids.dim() != 2:
+        raise ValueError("doc_starts_from_eos: input_ids must be [batch, seqlen]")
+    B, S = input_ids.shape
+    opens = torch.zeros((B, S), dtype=torch.bool, device=input_ids.device)
+    if S > 0:
+        opens[:, 0] = True
+        opens[:, 1:] = input_ids[:, :-1] == eos_token_id
+    idx = torch.arange(S, device=input_ids.device, dtype=torch.int32).expand(B, S)
+    start = torch.where(opens, idx, torch.zeros_like(idx))
+    return torch.cummax(start, dim=1).values.to(torch.int32)
+
+
+def doc_starts_from_lengths(lengths, S, check=False, device=None):
+    """doc_start int32 [B, S] from the document lengths of each row: `lengths` is a list of B lists (or one list,
+    B = 1), or an integer tensor [B, N] padded with zeros; each row's lengths sum to S. check=True validates the
+    result on the device (non-decreasing, doc_start[b, 0] == 0, doc_start[b, i] <= i, lengths summing to S): one
+    synchronisation, off by default."""
+    if not torch.is_tensor(lengths):
+        one_row = len(lengths) == 0 or not isinstance(lengths[0], (list, tuple))
+        rows = [list(lengths)] if one_row else [list(r) for r in lengths]
+        n = max(1, max(len(r) for r in rows))
+        lengths = torch.tensor([r + [0] * (n - len(r)) for r in rows], dtype=torch.int64, device=device)
+    elif device is not None:
+        lengths = lengths.to(device)
+    if lengths.dim() != 2:
+        raise ValueError("doc_starts_from_lengths: lengths must be [batch, documents]")
+    lengths = lengths.to(torch.int64)
+    ends = torch.cumsum(lengths, dim=1)                       # [B, N]: one past each document
+    pos = torch.arange(S, device=lengths.device).expand(lengths.shape[0], S).contiguous()
+    doc = torch.searchsorted(ends, pos, right=True).clamp_(max=lengths.shape[1] - 1)  # document of each token
+    start = torch.gather(ends - lengths, 1, doc).to(torch.int32)
+    if check:
+        ok = (lengths >= 0).all() & (ends[:, -1] == S).all() & check_doc_start(start, sync=False)
+        if not bool(ok):
+            raise ValueError("doc_starts_from_lengths: the lengths of a row must be non-negative and sum to S")
+    return start
+
+
+def check_doc_start(doc_start, sync=True):
+    """doc_start[b, 0] == 0, doc_start[b, i] <= i and non-decreasing along the sequence (a 0-dim bool tensor;
+    sync=True: a Python bool, one synchronisation)."""
+    S = doc_start.shape[1]
+    idx = torch.arange(S, device=doc_start.device, dtype=doc_start.dtype)
+    ok = (doc_start >= 0).all() & (doc_start <= idx).all() & (doc_start[:, 1:] >= doc_start[:, :-1]).all()
+    if S > 0:
+        ok = ok & (doc_start[:, 0] == 0).all()
+    return bool(ok) if sync else ok
+
+
+def doc_bounds(doc_start):
+    """int32 [2, B, S]: plane 0 = doc_start, plane 1 = doc_end (one past the last token of the document that holds
+    each token), so that the same mask reads from the key side as j <= i < doc_end[b, j]. Plain torch; compute it
+    once per micro-batch and share it among the layers."""
+    if doc_start.dim() != 2 or doc_start.dtype not in (torch.int32, torch.int64):
+        raise ValueError("doc_bounds: doc_start must be an integer tensor [batch, seqlen]")
+    B, S = doc_start.shape
+    start = doc_start.to(torch.int32)
+    # token i is the last of its document iff the next token opens one: doc_end = the next such position + 1
+    nxt = torch.full((B, S), S, dtype=torch.int32, device=start.device)
+    if S > 1:
+        idx = torch.arange(1, S, device=start.device, dtype=torch.int32).expand(B, S - 1)
+        opens = start[:, 1:] == idx                       # token i (>= 1) opens a document: it ends the one before at i
+        nxt[:, :-1] = torch.where(opens, idx, nxt[:, :-1])
+    end = torch.flip(torch.cummin(torch.flip(nxt, dims=(1,)), dim=1).values, dims=(1,))
+    return torch.stack((start, end.to(torch.int32))).contiguous()
+
+
 def attention_block_fwd(q, k, v, softmax_scale, causal, o_t=None, rope_q=None):
     """O [B,Sq,Hq,D] bf16 and LSE [B,Hq,Sq] fp32 (natural log) of softmax(scale*QK^T [+causal]) V.
     o_t (optional, bf16 [Hq*D, >= B*Sq] with unit column stride) also receives O transposed.
