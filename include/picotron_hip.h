@@ -45,6 +45,8 @@
  *                                 gradient accumulation (data_parallel.py:131 / autograd's grad += dW)
  *   pico_transpose_bf16       <- no reference call: lays out x^T / W^T for the faster hipBLASLt forms of
  *                                 the nn.Linear wgrad / dgrad GEMMs (ref picotron/model.py nn.Linear)
+ *   pico_kv_append, pico_attn_decode
+ *                             <- no reference call: KV-cache generation (picotron_amd/generate.py)
  *
  * Conventions: all pointers are device pointers allocated by the caller (kernels never
  * allocate); bf16 tensors are passed as raw 16-bit storage; `stream` is a hipStream_t
@@ -444,6 +446,42 @@ int pico_ce_vp_grad(const void* logits, int64_t ld, const int64_t* target, const
  * stride ld_dst (elements). rows, cols, ld_src, ld_dst multiples of 8; pointers 16-byte aligned. */
 int pico_transpose_bf16(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t rows, int64_t cols,
                         void* stream);
+
+/* ---- Generation: fused RoPE + KV-cache append, split-KV decode attention (no reference call: the reference
+ * has no sampling path) ----
+ * Caches are bf16 views [batch, heads_kv, s_max, head_dim] with unit last stride; k_strides / v_strides are their
+ * element strides {batch, head, position} (slices of a larger [layers, ...] allocation are fine). head_dim is 64 or
+ * 128, heads_q a multiple of heads_kv, every stride a multiple of 8 elements, every pointer 16-byte aligned; a
+ * violation returns PICO_EINVAL with a message.
+ *
+ * pico_kv_append: qkv is the fused q|k|v projection output, token (b, t) at qkv + b * batch_stride + t *
+ *   token_stride, holding heads_q q heads, heads_kv k heads and heads_kv v heads of head_dim elements. With p =
+ *   pos[b] + t (pos: DEVICE int32 [batch]): q is rotated in place with row p of the cos / sin tables ([table_rows,
+ *   >= head_dim / 2] bf16, row stride cs_stride), k is rotated with row p and stored at k_cache[b, :, p, :], v is
+ *   copied to v_cache[b, :, p, :]. The rotation is pico_rope's arithmetic bit for bit. A token with p outside
+ *   [0, min(s_max, table_rows)) is skipped whole (no q write, no cache write). Timed under PICO_K_ROPE.
+ *
+ * pico_attn_decode: one query per sequence. q[b, h] at q + b * q_strides[0] + h * q_strides[1] (head_dim bf16,
+ *   already rotated), seqlens DEVICE int32 [batch] -> o [batch, heads_q, head_dim] bf16 and lse [batch, heads_q]
+ *   fp32 (natural log), both contiguous, of softmax(softmax_scale q K^T) V over keys [0, min(seqlens[b], s_max)).
+ *   seqlens[b] <= 0 gives o = 0, lse = -inf; cache contents at or beyond the length are never read. One workgroup
+ *   serves the heads_q / heads_kv (at most 8; more is refused) query heads of a kv head over a chunk of split_keys
+ *   keys and writes an fp32 partial to the workspace; a second kernel combines a row's chunks in chunk order. No
+ *   atomics, no inter-workgroup waiting: the same inputs and split_keys give the same bits, and a row's result does
+ *   not depend on the other rows. split_keys <= 0 selects pico_attn_decode_split_keys (a host rule on the shape
+ *   and the CU count, never on the device lengths). workspace: pico_attn_decode_workspace_bytes for the same
+ *   arguments (-1 for bad arguments). Timed under PICO_K_ATTN_FWD (chunks) and PICO_K_ATTN_MERGE (combine). */
+int pico_kv_append(void* qkv, int64_t batch_stride, int64_t token_stride, const void* cos, const void* sin,
+                   int64_t cs_stride, int64_t table_rows, const int32_t* pos, void* k_cache, const int64_t* k_strides,
+                   void* v_cache, const int64_t* v_strides, int64_t batch, int64_t tokens, int64_t heads_q,
+                   int64_t heads_kv, int64_t s_max, int64_t head_dim, void* stream);
+int64_t pico_attn_decode_split_keys(int64_t batch, int64_t heads_kv, int64_t s_max, int64_t head_dim);
+int64_t pico_attn_decode_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t s_max,
+                                         int64_t head_dim, int64_t split_keys);
+int pico_attn_decode(const void* q, const int64_t* q_strides, const void* k_cache, const int64_t* k_strides,
+                     const void* v_cache, const int64_t* v_strides, const int32_t* seqlens, void* o, float* lse,
+                     void* workspace, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t s_max,
+                     int64_t head_dim, float softmax_scale, int64_t split_keys, void* stream);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,13 @@ _SIGNATURES = {
     "pico_ce_vp_grad": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
                                        c_vp]),
     "pico_transpose_bf16": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "pico_kv_append": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64),
+                                      c_vp, ctypes.POINTER(c_i64), c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "pico_attn_decode_split_keys": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    "pico_attn_decode_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "pico_attn_decode": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
+                                        ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                        c_i64, ctypes.c_float, c_i64, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
