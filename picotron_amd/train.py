@@ -152,6 +152,16 @@ def train_step(model, data_loader, device, graphs=None, sync_loss=True):
     return value
 
 
+def _capturing(graph, pool=None):
+    """torch.cuda.graph with the capture's error mode thread-local. In the default global mode an event query from
+    ANY thread is an error while a capture is open, and an RCCL process group's watchdog thread polls the events of
+    its collectives every 100 ms: a poll that fell into a capture got "operation not permitted when stream is
+    capturing", and the exception in that thread ended the process (seen in the DataParallelBucket + graph tests).
+    Thread-local mode keeps the check for the capturing thread and leaves other threads alone; the captured graph is
+    the same (torch's own graph trees capture this way for the same reason)."""
+    return torch.cuda.graph(graph, pool=pool, capture_error_mode="thread_local")
+
+
 class MicroBatchGraph:
     """A training micro-batch (forward, mean CE / grad_acc, backward) captured once as a HIP graph
     and replayed: the ~330 kernels of a SmolLM-1.7B micro-batch then launch back to back instead of
@@ -186,7 +196,7 @@ class MicroBatchGraph:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with _capturing(self.graph):
             self._fwd_bwd()
         torch.cuda.synchronize()
         self.zero_grads()
@@ -322,16 +332,16 @@ class PipelinedMicroBatchGraph:
         torch.cuda.synchronize()
         if split:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _capturing(g):
                 self._body(inp, tgt, "head")
             head_state = WP.pending_state()
             g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, pool=g.pool()):
+            with _capturing(g2, pool=g.pool()):
                 self._body(inp, tgt, "tail")
             tail_state = WP.pending_state()
         else:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _capturing(g):
                 self._body(inp, tgt)
         torch.cuda.synchronize()
         self.zero_grads()

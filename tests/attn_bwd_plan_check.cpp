@@ -1,7 +1,11 @@
 // Host-only sweep of the split attention backward's plan (picotron_amd/csrc/attn_bwd_plan.h), built and run by
 // tests/test_attn_bwd_plan.py: every shape x knob x CU count below must give a consistent SplitPlan. Exits
 // non-zero with the failing shape printed.
+// With arguments it prints plans instead (tests/test_attn_tiles_host.py): every 11 integers
+//   head_dim causal batch seqlen_q seqlen_k heads_q heads_kv kvp waves groups cus      (knobs: -1 = PICO_SEL_AUTO)
+// give one line "kvp waves kvb minb hsplit grp_n q_front q_grid kv_grid bytes".
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "../picotron_amd/csrc/attn_bwd_plan.h"
@@ -44,7 +48,29 @@ static const char* check(const pico_attn_args& a, const SplitEnv& e, const Split
   return nullptr;
 }
 
-int main() {
+static int print_plans(int argc, char** argv) {
+  if ((argc - 1) % 11) return 3;
+  for (int i = 1; i < argc; i += 11) {
+    long x[11];
+    for (int j = 0; j < 11; ++j) x[j] = strtol(argv[i + j], nullptr, 10);
+    pico_attn_args a;
+    memset(&a, 0, sizeof a);
+    a.head_dim = x[0], a.causal = (int)x[1], a.batch = x[2], a.seqlen_q = x[3], a.seqlen_k = x[4];
+    a.heads_q = x[5], a.heads_kv = x[6];
+    const SplitEnv e{(int)x[10], (int)x[7], (int)x[8], (int)x[9], 0};
+    const SplitPlan p = split_plan(&a, e);
+    if (const char* why = check(a, e, p)) {
+      printf("FAIL %s\n", why);
+      return 1;
+    }
+    printf("%d %d %d %d %d %d %d %lld %lld %lld\n", (int)p.kvp, p.waves, p.kvb, p.minb, p.hsplit, p.grp.n, p.q_front,
+           (long long)p.q_grid, (long long)p.kv_grid, (long long)p.bytes);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return print_plans(argc, argv);
   const int dims[] = {64, 128}, seqs[] = {1, 31, 32, 64, 200, 256, 1024, 1536, 1537, 2048, 4096, 4097};
   const int bhs[][2] = {{1, 1}, {3, 1}, {4, 16}, {5, 16}, {3, 100}};  // batch x heads_kv = 1, 3, 64, 80, 300
   const int sel3[] = {PICO_SEL_AUTO, 0, 1}, selw[] = {PICO_SEL_AUTO, 4, 8};

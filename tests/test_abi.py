@@ -501,3 +501,15 @@ def test_kernel_selection_knobs(lib):
     assert lib.pico_select(99, 0) == -2 and lib.pico_select(-1, 0) == -2
     with pytest.raises(ValueError):
         _lib.select(99, 0)
+
+
+def test_graph_captures_are_thread_local():
+    """Every graph capture of the training step goes through train._capturing, whose capture error mode is
+    thread-local: in the global mode an event query by a process group's watchdog thread during a capture is an
+    error that ends the process (a DataParallelBucket + graph test once aborted the whole GPU suite that way)."""
+    import inspect
+    from picotron_amd import train
+    src = inspect.getsource(train)
+    calls = re.findall(r"torch\.cuda\.graph\(([^\n]*)", src)
+    assert len(calls) == 1 and 'capture_error_mode="thread_local"' in calls[0], calls
+    assert src.count("with _capturing(") >= 4

@@ -369,12 +369,15 @@ def test_attention_gqa_head_split(B, Hq, Hkv):
 
 @pytest.mark.parametrize("S,Hq,Hkv,causal,mode", [(2300, 2, 2, True, "bf16"), (2304, 4, 2, False, "bf16"),
                                                    (2300, 2, 1, True, "f32acc"), (2304, 2, 2, True, "rope"),
-                                                   (2304, 64, 64, True, "rope")])  # one workgroup per key block: dK RoPE^-1 in the last group
+                                                   (2304, 64, 64, True, "rope")])  # one workgroup per key block: dK RoPE^-1 in its epilogue
 def test_attention_bwd_d128_key_block_groups(S, Hq, Hkv, causal, mode):
-    """head_dim 128 past PICO_BWD_KB_CAP (8) key blocks: the fused backward runs its key blocks in groups with a
-    bounded number of dQ slabs, the groups' sums added into an fp32 dQ. vs an fp32 torch
-    reference: bf16 dQ, the caller's fp32 accumulator (ring mode), and the fused RoPE^-1 (rotation per
-    group, dK rotated once after the last)."""
+    """head_dim 128 at 18 key blocks of 128 keys (the name is from a fused backward that ran such lengths in key-block
+    groups; pico_attn_bwd always takes the split path now). By attn_bwd_plan.h at 256 CUs the four B 1 cases have
+    36 or 18 key blocks for 256 slots, so each key block's tile list is split 8 ways (hsplit 8: fp32 partials summed
+    and, in the rope case, rotated by attn_bwd_dkv_kernel); the 64-head case runs the plain grid of 1152 workgroups
+    with hsplit 1 (18 blocks are more than its 4 groups hold), dK rotated in the kernel's epilogue, and a dQ front
+    of 10 blocks. vs an fp32 torch reference: bf16 dQ, the caller's fp32 accumulator (ring mode), the fused
+    RoPE^-1."""
     from picotron_amd.model import get_cos_sin
     ops = _ops()
     torch.manual_seed(S + Hq + Hkv)
@@ -416,9 +419,9 @@ def test_attention_bwd_d128_key_block_groups(S, Hq, Hkv, causal, mode):
 
 
 @pytest.mark.parametrize("B,Sq,Sk,Hq,Hkv,causal,mode", [
-    (2, 1024, 1024, 8, 8, True, "bf16"),     # C2 slice, block groups
-    (1, 1000, 1000, 8, 2, True, "bf16"),     # ragged, GQA 4
-    (4, 1024, 1024, 32, 8, True, "bf16"),    # GQA 4 at a small grid: key blocks split over workgroups (hsplit)
+    (2, 1024, 1024, 8, 8, True, "bf16"),     # C2 slice: 128 key blocks for 512 slots, plain grid with hsplit 4
+    (1, 1000, 1000, 8, 2, True, "bf16"),     # ragged, GQA 4 (hsplit 8)
+    (4, 1024, 1024, 32, 8, True, "bf16"),    # GQA 4 at a small grid: key blocks split over workgroups (hsplit 2)
     (1, 1536, 1536, 4, 4, True, "rope"),     # the causal default's last length, fused RoPE^-1
     (1, 2049, 2049, 2, 2, True, "f32acc"),   # past it (default: the 32-row kernel), caller's fp32 dQ
     (1, 2048, 2048, 4, 4, False, "bf16"),    # non-causal 2048: the 8-wave default
@@ -433,8 +436,8 @@ def test_attention_bwd_d64_kv_kernels(monkeypatch, B, Sq, Sk, Hq, Hkv, causal, m
 
 
 @pytest.mark.parametrize("B,Sq,Sk,Hq,Hkv,causal,mode", [
-    (4, 1024, 1024, 16, 16, True, "bf16"),   # C4 per tp-2 rank (Llama-2-7B), micro-batch 4
-    (1, 1000, 1000, 8, 2, True, "bf16"),     # ragged, GQA 4, key blocks split over workgroups (hsplit)
+    (4, 1024, 1024, 16, 16, True, "bf16"),   # C4 per tp-2 rank (Llama-2-7B), micro-batch 4: 4 block groups
+    (1, 1000, 1000, 8, 2, True, "bf16"),     # ragged, GQA 4, key blocks split over workgroups (hsplit 8)
     (2, 1024, 1024, 32, 8, True, "rope"),    # GQA 4, fused RoPE^-1
     (1, 520, 520, 4, 4, True, "f32acc"),     # caller's fp32 dQ
     (2, 96, 200, 4, 4, False, "bf16"),       # cross lengths, non-causal
