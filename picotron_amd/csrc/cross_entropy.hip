@@ -13,6 +13,7 @@
 // between the max and the sum-of-exp passes, so each pass reads the row from HBM once.
 // fp32 math throughout (torch: fp32 opmath inside log_softmax, bf16 log-probs in between).
 #include "common.h"
+#include "rowwise_plan.h"
 
 // PICO_CE_THREADS: threads per logits row in the fused forward+gradient kernel (A/B build variants)
 #ifndef PICO_CE_THREADS
@@ -117,7 +118,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ 
 // Forward that also produces the gradient in place: lse, loss as ce_fwd_kernel, then the row (still in
 // registers) is overwritten with dlogits = (softmax - onehot(t)) * (*gscale) (0 for ignored rows). One
 // read + one write of the logits instead of fwd read + bwd read + bwd write; the caller applies the
-// upstream gradient later (it scales the LM-head GEMMs' results, not the logits).
+// upstream gradient later (it scales the LM-head GEMMs' results, not the logits). *gscale must be >= 0: it is
+// folded in as log2(*gscale), and a negative value makes the whole row NaN (pico_ce_count refuses one).
 template <int NCH, int NT>
 __global__ __launch_bounds__(NT) void ce_fwd_grad_kernel(bf16_t* __restrict__ logits, int64_t ld,
                                                           const int64_t* __restrict__ target, float* __restrict__ lse,
@@ -179,12 +181,7 @@ __global__ __launch_bounds__(NT) void ce_fwd_grad_kernel(bf16_t* __restrict__ lo
   }
 }
 
-int nch_for(int64_t vocab, int nt = 256) {
-  const int64_t per = (vocab / 8 + nt - 1) / nt;
-  for (int n : {2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64})
-    if (per <= n) return n;
-  return -1;
-}
+using rw::nch_for;
 
 }  // namespace
 
@@ -212,6 +209,7 @@ extern "C" int pico_cross_entropy_fwd(const void* logits, int64_t ld, const int6
   PICO_REQUIRE(rows < (1ll << 31), "pico_cross_entropy_fwd: too many rows");
   if (rows == 0) return 0;
   PICO_REQUIRE(logits && target && lse && loss, "pico_cross_entropy_fwd: null pointer");
+  PICO_REQUIRE((uintptr_t)logits % 16 == 0, "pico_cross_entropy_fwd: logits must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   CE_SWITCH(nch, PICO_TRY(pico_launch(PICO_K_CE_FWD, "cross_entropy_fwd", ce_fwd_kernel<N>, dim3((int)rows), dim3(256), 0, s, (const bf16_t*)logits, ld, target, lse, loss,
                                                                         (int)vocab, ignore_index)))
@@ -228,6 +226,7 @@ extern "C" int pico_cross_entropy_fwd_grad(void* logits, int64_t ld, const int64
   PICO_REQUIRE(rows < (1ll << 31), "pico_cross_entropy_fwd_grad: too many rows");
   if (rows == 0) return 0;
   PICO_REQUIRE(logits && target && lse && loss && grad_scale, "pico_cross_entropy_fwd_grad: null pointer");
+  PICO_REQUIRE((uintptr_t)logits % 16 == 0, "pico_cross_entropy_fwd_grad: logits must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   CE_SWITCH(nch, PICO_TRY(pico_launch(PICO_K_CE_FWD, "cross_entropy_fwd_grad", ce_fwd_grad_kernel<N, PICO_CE_THREADS>, dim3((int)rows), dim3(PICO_CE_THREADS), 0, s, (bf16_t*)logits, ld, target, lse, loss,
                                                                              grad_scale, (int)vocab, ignore_index)))
@@ -240,9 +239,14 @@ extern "C" int pico_cross_entropy_bwd(const void* logits, int64_t ld, const int6
   PICO_REQUIRE(rows >= 0 && vocab > 0 && vocab % 8 == 0 && ld % 8 == 0 && ldd % 8 == 0,
                "pico_cross_entropy_bwd: vocab and row strides must be multiples of 8");
   const int nch = nch_for(vocab);
+  PICO_REQUIRE(ld >= vocab, "pico_cross_entropy_bwd: ld (%lld) must be >= vocab", (long long)ld);
+  PICO_REQUIRE(ldd >= vocab, "pico_cross_entropy_bwd: ldd (%lld) must be >= vocab", (long long)ldd);
   PICO_REQUIRE(nch > 0, "pico_cross_entropy_bwd: vocab %lld too large", (long long)vocab);
+  PICO_REQUIRE(rows < (1ll << 31), "pico_cross_entropy_bwd: too many rows");
   if (rows == 0) return 0;
   PICO_REQUIRE(logits && target && lse && grad_scale && dlogits, "pico_cross_entropy_bwd: null pointer");
+  PICO_REQUIRE((uintptr_t)logits % 16 == 0 && (uintptr_t)dlogits % 16 == 0,
+               "pico_cross_entropy_bwd: logits and dlogits must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   CE_SWITCH(nch, PICO_TRY(pico_launch(PICO_K_CE_BWD, "cross_entropy_bwd", ce_bwd_kernel<N>, dim3((int)rows), dim3(256), 0, s, (const bf16_t*)logits, ld, target, lse,
                                                                         grad_scale, (bf16_t*)dlogits, ldd, (int)vocab,
@@ -493,6 +497,7 @@ __global__ __launch_bounds__(CE_NT) void ce_mean_kernel(const float* __restrict_
 extern "C" int pico_ce_count(const int64_t* target, int64_t n, int64_t ignore_index, float grad_scale, float* stats,
                              void* stream) {
   PICO_REQUIRE(target && stats && n >= 0, "pico_ce_count: bad arguments");
+  PICO_REQUIRE(grad_scale >= 0.f, "pico_ce_count: grad_scale (%g) must be >= 0", (double)grad_scale);
   PICO_TRY(pico_launch(PICO_K_CE_FWD, "ce_count", ce_count_kernel, dim3(1), dim3(CE_NT), 0, (hipStream_t)stream, target, n, ignore_index, grad_scale, stats));
   return 0;
 }
@@ -535,9 +540,7 @@ extern "C" int pico_ce_scale_grad(void* dx, int64_t n, const void* upstream, int
   PICO_REQUIRE(dx && upstream && n >= 0, "pico_ce_scale_grad: bad arguments");
   PICO_REQUIRE((uintptr_t)dx % 16 == 0, "pico_ce_scale_grad: dx must be 16-byte aligned");
   if (n == 0) return 0;
-  int64_t nb = (n / 8 + 255) / 256;
-  if (nb < 1) nb = 1;
-  if (nb > 4096) nb = 4096;
-  PICO_TRY(pico_launch(PICO_K_CE_BWD, "ce_scale_grad", scale_by_dev_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dx, n, upstream, upstream_f32, nonunit));
+  const int nb = rw::scale_grid(n);
+  PICO_TRY(pico_launch(PICO_K_CE_BWD, "ce_scale_grad", scale_by_dev_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dx, n, upstream, upstream_f32, nonunit));
   return 0;
 }

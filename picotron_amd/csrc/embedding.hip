@@ -7,9 +7,11 @@
 // elements = 200 MB written, then 600 MB for the accumulate) and sizes its unique/partition work
 // on the host, which a graph replay cannot redo. Here the caller stable-sorts the token ids
 // (torch.sort, device-only), and one workgroup per sorted position that starts a run of equal ids
-// sums that run's dy rows in position order (fp32) and updates only that id's row in place:
+// sums that run's dy rows in position order (fp32, in blocks of 64 positions) and updates only that id's row in place:
 //   grad[id] = (grad[id] + sum) * scale        (bf16 or fp32 gradient; one rounding)
-// Every row is owned by exactly one workgroup (no atomics); the summation order is fixed.
+// Every row is owned by exactly one workgroup (no atomics); the summation order is fixed: position order within
+// blocks of 64 positions of a run, each block summed from zero, then the block sums in order (a run of up to 64
+// positions is one plain position-order chain).
 // Bytes: dy read once (T * H * 2) + touched rows read and written once.
 //
 // pico_sort_ids replaces the torch.sort(ids, stable=True) in front of it (ATen: index copies, an
@@ -17,6 +19,7 @@
 // bitonic-sorts 32-bit keys (id << 13 | position) in LDS, three stages per barrier. Positions are unique, so the order of equal
 // ids is their position order (the stable order), and the result is bit-identical to torch's.
 #include "common.h"
+#include "rowwise_plan.h"
 
 namespace {
 
@@ -28,12 +31,22 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __res
   const int64_t b = blockIdx.x;
   const int64_t id = sorted_ids[b];
   if (b > 0 && sorted_ids[b - 1] == id) return;  // not the start of a run
-  for (int64_t c = (int64_t)threadIdx.x * 8; c < dim; c += 256 * 8) {
+  for (int64_t c = (int64_t)threadIdx.x * 8; c < dim; c += rw::EMB_COLS_PER_TRIP) {
+    // a run is summed in blocks of EMB_RUN_BLOCK positions, each from zero, and the block sums are added in order:
+    // one long chain over a run of thousands (a padding token) loses sqrt(run) roundings at the magnitude of the
+    // whole sum (measured on the fp32 restatement: 12 fp32 ulps of sum|dy| at a run of 8192, under 2 in blocks).
+    // Runs of up to one block keep their bits (0 + x is exact).
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int64_t j = b; j < n && sorted_ids[j] == id; ++j) {
-      const u16x8 v = *reinterpret_cast<const u16x8*>(dy + sorted_pos[j] * dim + c);
+    for (int64_t j = b; j < n && sorted_ids[j] == id;) {
+      float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      const int64_t je = j + rw::EMB_RUN_BLOCK;
+      for (; j < je && j < n && sorted_ids[j] == id; ++j) {
+        const u16x8 v = *reinterpret_cast<const u16x8*>(dy + sorted_pos[j] * dim + c);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) acc[k] += bf2f(v[k]);
+        for (int k = 0; k < 8; ++k) part[k] += bf2f(v[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] += part[k];
     }
     if constexpr (F32) {
       f32x4* g = reinterpret_cast<f32x4*>((float*)grad + id * dim + c);

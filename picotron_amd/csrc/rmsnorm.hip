@@ -11,10 +11,16 @@
 // is read from HBM exactly once. Algorithmic bytes: fwd 2*cols*2 B + 4 B per row,
 // bwd 3*cols*2 B + 4 B per row (+ the small fp32 dw partials).
 #include "common.h"
+#include "rowwise_plan.h"
 
 namespace {
 
-constexpr int WAVES = 4;
+using rw::bwd_blocks;
+using rw::bwd_waves;
+using rw::maxc_for;
+using rw::PREV_COLS;  // chained dw: column slots per workgroup (cpw <= 16)
+
+constexpr int WAVES = rw::RMS_FWD_WAVES;
 
 PICO_DEV float wave_sum(float v) { return wave_sum_dpp(v); }
 
@@ -197,7 +203,6 @@ struct DwPrev {
   int nb, cols, cpw, mode;
   float scale;
 };
-constexpr int PREV_COLS = 16;  // column slots per workgroup (cpw <= 16)
 
 // Backward: dx = rstd * (g - xhat * mean(g * xhat)), g = dy * w, xhat = x * rstd;
 // dw partial per workgroup (deterministic two-stage reduction, no atomics).
@@ -325,8 +330,6 @@ __global__ __launch_bounds__(NW * 64) void rmsnorm_bwd_kernel(const bf16_t* __re
   }
 }
 
-constexpr int bwd_waves(int maxc) { return maxc <= 2 ? 16 : (maxc == 4 ? 8 : 4); }
-
 template <int M>
 int launch_rmsnorm_bwd(const void* dy, const void* dres, const void* x, const void* w, const float* rstd, void* dx,
                        float* part, int64_t rows, int c, int nb, const DwPrev& prev, hipStream_t s) {
@@ -381,27 +384,6 @@ __global__ __launch_bounds__(256) void rmsnorm_dw_kernel(const float* __restrict
   }
 }
 
-int maxc_for(int64_t cols) {
-  int64_t c = (cols + 511) / 512;
-  if (c <= 1) return 1;
-  if (c <= 2) return 2;
-  if (c <= 4) return 4;
-  if (c <= 8) return 8;
-  if (c <= 16) return 16;
-  return -1;
-}
-
-
-#ifndef PICO_RMS_BWD_MAXB
-#define PICO_RMS_BWD_MAXB 256
-#endif
-
-int bwd_blocks(int64_t rows, int64_t cols) {  // one workgroup per CU at most: few dw partial rows
-  const int nw = bwd_waves(maxc_for(cols));
-  int64_t nb = (rows + nw - 1) / nw;
-  return (int)(nb < PICO_RMS_BWD_MAXB ? nb : PICO_RMS_BWD_MAXB);
-}
-
 }  // namespace
 
 extern "C" {
@@ -446,6 +428,8 @@ int pico_rmsnorm_fwd(const void* x, const void* residual, const void* weight, vo
                (long long)cols);
   const int mc = maxc_for(cols);
   PICO_REQUIRE(mc > 0, "pico_rmsnorm_fwd: cols=%lld > 8192 unsupported", (long long)cols);
+  PICO_REQUIRE((((uintptr_t)x | (uintptr_t)residual | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)residual_out) & 15) == 0,
+               "pico_rmsnorm_fwd: x, residual, weight, y and residual_out must be 16-byte aligned");
   if (rows == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(pico_cdiv(rows, WAVES)), block(256);
@@ -514,13 +498,15 @@ int pico_rmsnorm_bwd_chain(const void* dy, const void* dresidual, const void* x,
                (long long)rows, (long long)cols);
   const int mc = maxc_for(cols);
   PICO_REQUIRE(mc > 0 && mc <= 8, "pico_rmsnorm_bwd: cols=%lld > 4096 unsupported", (long long)cols);
+  PICO_REQUIRE((((uintptr_t)dy | (uintptr_t)dresidual | (uintptr_t)x | (uintptr_t)weight | (uintptr_t)dx) & 15) == 0,
+               "pico_rmsnorm_bwd: dy, dresidual, x, weight and dx must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int nb = bwd_blocks(rows, cols);
   DwPrev prev{nullptr, nullptr, 0, 0, 0, 0, 1.f};
   if (prev_part) {
     PICO_REQUIRE(prev_dweight && prev_mode >= 0 && prev_mode <= 2 && prev_nb > 0 && prev_nb <= 256 && prev_cols > 0,
                  "pico_rmsnorm_bwd_chain: bad previous partials");
-    const int64_t cpw = (prev_cols + nb - 1) / nb;
+    const int64_t cpw = rw::chain_cpw(prev_cols, nb);
     if (cpw <= PREV_COLS) {
       prev = DwPrev{prev_part, prev_dweight, (int)prev_nb, (int)prev_cols, (int)cpw, prev_mode, prev_scale};
     } else {  // too many columns for this grid: reduce them in their own launch first

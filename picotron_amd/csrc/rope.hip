@@ -9,29 +9,21 @@
 // Each thread owns 8 consecutive rotary pairs: two 16-byte loads of x (i and i + D/2), two of the
 // tables, two 16-byte stores. Algorithmic bytes: 2 * 2 B per element of x (tables are L2-resident).
 #include "common.h"
+#include "rowwise_plan.h"
 
 namespace {
 
-// n / d for 0 <= n < 2^31 by a multiply-high (round-up method; m and l precomputed on the host): the rope
-// thread's index decomposition otherwise costs three 32-bit integer divisions (~40 VALU each), a sizeable
-// share of a kernel that issues four 16-byte loads per thread
-struct FastDiv {
-  unsigned d, m, l;
-};
-FastDiv make_fastdiv(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  f.l = 0;
-  while ((1ull << f.l) < d) ++f.l;
-  f.m = (unsigned)((((1ull << 32) * ((1ull << f.l) - d)) / d) + 1);
-  return f;
-}
-PICO_DEV unsigned fdiv(unsigned n, const FastDiv& f) { return (__umulhi(n, f.m) + n) >> f.l; }
+using rw::FastDiv;  // n / d for 0 <= n < 2^31 by a multiply-high (rowwise_plan.h)
+using rw::fdiv;
+using rw::make_fastdiv;
 
 // t enumerates (b, s, head, vector) with the vector fastest, so a wave's loads and stores cover whole rows.
 // (Measured and removed: two heads per thread sharing the cos / sin loads, 5.7 vs 5.6 us; streaming loads,
 // 9.6 vs 9.1 us in the step.)
-__global__ __launch_bounds__(256) void rope_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ out,
+// x / out may be the same buffer (the rotation in place of q|k inside the qkv GEMM's output): no __restrict__ on
+// them. A thread reads both of its 16-byte vectors (i and i + D/2) before it writes either, and no other thread
+// touches them.
+__global__ __launch_bounds__(256) void rope_kernel(const bf16_t* x, bf16_t* out,
                                                    const bf16_t* __restrict__ cosp, const bf16_t* __restrict__ sinp,
                                                    int64_t total, FastDiv fv, FastDiv fh, FastDiv fs, int half,
                                                    int64_t xs0, int64_t xs1, int64_t xs2, int64_t os0, int64_t os1,
@@ -85,9 +77,8 @@ extern "C" int pico_rope(const void* x, void* out, const void* cos, const void* 
   PICO_REQUIRE(total < (int64_t)0x7fffffff, "pico_rope: tensor too large");
   if (total == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  int64_t nb = (total + 255) / 256;
-  if (nb > 8192) nb = 8192;
-  PICO_TRY(pico_launch(PICO_K_ROPE, "rope", rope_kernel, dim3((int)nb), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out,
+  const int nb = rw::rope_grid(total);
+  PICO_TRY(pico_launch(PICO_K_ROPE, "rope", rope_kernel, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out,
                        (const bf16_t*)cos, (const bf16_t*)sin, total, make_fastdiv((unsigned)(head_dim / 16)),
                        make_fastdiv((unsigned)heads), make_fastdiv((unsigned)seqlen), (int)(head_dim / 2), xst[0],
                        xst[1], xst[2], ost[0], ost[1], ost[2], cs_stride, conjugate ? -1.f : 1.f));

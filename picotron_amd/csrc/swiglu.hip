@@ -7,10 +7,22 @@
 // straight into the two halves of the fused GEMM's input gradient.
 // Algorithmic bytes per element: fwd 3 * 2 B, bwd 5 * 2 B.
 #include "common.h"
+#include "rowwise_plan.h"
 
 namespace {
 
-PICO_DEV float sigmoidf_(float g) { return 1.f / (1.f + __expf(-g)); }
+// sigma(g) = 1 / (1 + exp(-g)). Below g = -88.7 exp(-g) overflows fp32 and the quotient is 0, while silu(g) * u and
+// both gradients are still normal numbers there (89 e^-89 |u| ~ 2e-37 |u|): from -87 down sigma = e^g (to within
+// 1e-38 relative), taken as 2^64 e^g and scaled back so that the exp2 stays in the normal range. Below about
+// g = -87.3 that value is an fp32 denormal: it relies on the fp32 denormal support the library is built with (no
+// flush-to-zero flag), and loses significand bits as g falls; by the point where that loss reaches the bf16
+// result (g near -100, sigma < 2^-144) the outputs are far below 2^-120 for any bf16 u and dh the tests use.
+// Unchanged bits for g >= -87.
+PICO_DEV float sigmoidf_(float g) {
+  const float s = 1.f / (1.f + __expf(-g));
+  const float tail = __builtin_amdgcn_exp2f(__builtin_fmaf(g, 1.4426950408889634f, 64.f)) * 0x1p-64f;
+  return g < -87.f ? tail : s;
+}
 
 PICO_DEV void swiglu_grad(float dh, float gf, float uf, float& dg, float& du) {
   const float sg = sigmoidf_(gf);
@@ -144,16 +156,8 @@ __global__ __launch_bounds__(256) void swiglu_bwd_scalar(const bf16_t* __restric
   }
 }
 
-int grid_for(int64_t work) {
-  int64_t nb = (work + 255) / 256;
-  if (nb < 1) nb = 1;
-  if (nb > 4096) nb = 4096;  // 256 CUs x 16 workgroups, grid-stride beyond
-  return (int)nb;
-}
-
-bool vec_ok(int64_t cols, int64_t is, int64_t os, const void* a, const void* b, const void* c) {
-  return cols % 8 == 0 && is % 8 == 0 && os % 8 == 0 && ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) % 16 == 0;
-}
+using rw::grid_for;
+using rw::vec_ok;
 
 }  // namespace
 

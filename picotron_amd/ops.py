@@ -37,6 +37,14 @@ def _need(t, name, dtype=_BF16):
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
 
 
+def _aligned16(t):
+    """t, or a copy of it in fresh (16-byte aligned) storage when t is a view at an odd storage offset: the
+    kernels' 16-byte vector accesses need it, and the entry points refuse anything else."""
+    if t is None or t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 # --------------------------------------------------------------------------------------------
 # RMSNorm  (flash_attn.ops.triton.layer_norm.layer_norm_fn with is_rms_norm=True)
 # --------------------------------------------------------------------------------------------
@@ -55,7 +63,7 @@ class _RMSNormFn(torch.autograd.Function):
             _NORM_PENDING.pop(x.device, None)
         shape = x.shape
         cols = shape[-1]
-        x2 = x.reshape(-1, cols).contiguous()
+        x2 = _aligned16(x.reshape(-1, cols).contiguous())
         rows = x2.shape[0]
         lib = _lib.load()
         y = torch.empty_like(x2)
@@ -64,12 +72,12 @@ class _RMSNormFn(torch.autograd.Function):
         res_out = None
         if residual is not None:
             _need(residual, "residual")
-            res2 = residual.reshape(-1, cols).contiguous()
+            res2 = _aligned16(residual.reshape(-1, cols).contiguous())
             res_out = torch.empty_like(x2)
-        w = weight.contiguous()
+        w = _aligned16(weight.contiguous())
         yt = None
-        if want_t and os.getenv("PICO_XT_WGRAD", "1") != "0" and cols in (1024, 2048) and rows % 32 == 0 and \
-                all(t is None or t.data_ptr() % 16 == 0 for t in (x2, res2, w)):
+        if want_t and os.getenv("PICO_XT_WGRAD", "1") != "0" and cols in (1024, 2048) and rows % 32 == 0:
+            # (x2, res2 and w are 16-byte aligned: _aligned16 above)
             # y^T as a by-product for the next projection's TT wgrad GEMM (no separate transpose pass), into the
             # projection's x^T pair buffer when its weight gradients are paired
             yt = _pair_xt(pair[0] if pair else None, cols, rows, x) if pair else None
@@ -101,10 +109,10 @@ class _RMSNormFn(torch.autograd.Function):
         x_eff, w, rstd = ctx.saved_tensors
         cols = ctx.shape[-1]
         rows = x_eff.shape[0]
-        dy2 = dy.reshape(-1, cols).contiguous()
+        dy2 = _aligned16(dy.reshape(-1, cols).contiguous())
         dres = None
         if ctx.prenorm and rest and rest[0] is not None:
-            dres = rest[0].reshape(-1, cols).contiguous()
+            dres = _aligned16(rest[0].reshape(-1, cols).contiguous())
         lib = _lib.load()
         dx = _pair_dy(ctx.pair_dy, rows, cols, x_eff)  # the producing projection's dy pair buffer (wgrad_pair)
         if dx is None:
@@ -703,6 +711,7 @@ class _CrossEntropyFn(torch.autograd.Function):
         rows, vocab = logits.shape
         if logits.stride(1) != 1:
             logits = logits.contiguous()
+        logits = _aligned16(logits)
         t = target.reshape(-1)
         if t.dtype != torch.int64:
             t = t.long()
@@ -747,7 +756,7 @@ class _LMHeadCEFn(torch.autograd.Function):
         H = x.shape[-1]
         x2 = x.reshape(-1, H)
         T, V = x2.shape[0], w.shape[0]
-        logits = torch.nn.functional.linear(x2, w)  # [T, V] bf16, becomes dlogits in place below
+        logits = torch.nn.functional.linear(x2, w)  # [T, V] bf16 (a fresh, aligned allocation), dlogits in place below
         t = target.reshape(-1)
         if t.dtype != torch.int64:
             t = t.long()
@@ -984,6 +993,8 @@ def lm_head_cross_entropy(x, w, target, ignore_index=-100, grad_scale=None, chun
         if loss_acc is not None:
             raise ValueError("lm_head_cross_entropy: loss_acc needs the chunked form (grad_scale=...)")
         return _LMHeadCEFn.apply(x, w, target, ignore_index)
+    if not float(grad_scale) >= 0.0:  # the CE kernel folds it in as log2(grad_scale): a negative one gives NaN rows
+        raise ValueError(f"lm_head_cross_entropy: grad_scale must be >= 0, got {grad_scale}")
     return _LMHeadCEChunkedFn.apply(x, w, target, ignore_index, float(grad_scale),
                                     ce_chunk_rows() if chunk is None else int(chunk), loss_acc)
 

@@ -291,7 +291,9 @@ def rope_tables(S, D, device="cpu", base=10000.0):
 
 
 # ------------------------------------------------------------------------------------------ guard bands
-_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8}
+_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8, torch.int64: torch.int64,
+        torch.int32: torch.int32}
+INT_GUARD = -0x5A5A5A5A  # guard value of integer buffers (token ids, targets): no valid index
 
 
 class Guards:
@@ -310,13 +312,15 @@ class Guards:
     def _new(self, shape, dtype):
         if dtype == torch.uint8:
             return torch.full(shape, 0xFF, dtype=dtype, device=self.dev)
+        if not dtype.is_floating_point:
+            return torch.full(shape, INT_GUARD, dtype=dtype, device=self.dev)
         return torch.full(shape, math.nan, dtype=dtype, device=self.dev)
 
-    def bshd(self, name, B, S, H, D, dtype=BF, data=None, fill=None):
-        """[B, S, H, D] view: g guard rows before and after every batch's sequence and one guard head. data: an
-        input (copied in); fill: an output interior starting at a constant; neither: an output full of NaN."""
+    def bshd(self, name, B, S, H, D, dtype=BF, data=None, fill=None, pad_heads=1):
+        """[B, S, H, D] view: g guard rows before and after every batch's sequence and pad_heads guard heads. data:
+        an input (copied in); fill: an output interior starting at a constant; neither: an output full of NaN."""
         g = self.g
-        buf = self._new((B, S + 2 * g, H + 1, D), dtype)
+        buf = self._new((B, S + 2 * g, H + pad_heads, D), dtype)
         view = buf[:, g:g + S, :H]
         inside = torch.zeros(buf.shape, dtype=torch.bool, device=self.dev)
         inside[:, g:g + S, :H] = True
@@ -336,6 +340,22 @@ class Guards:
         if data is not None:
             view.copy_(data.reshape(-1))
         return self._add(name, buf, view.view(shape) if shape else view, inside, data is None)
+
+    def mat(self, name, rows, cols, dtype=BF, data=None, ld=None, shift=0, inout=False):
+        """[rows, cols] view with row stride ld (default cols: row-contiguous) inside a flat buffer, 256 guard bytes
+        (+ shift elements: a deliberately unaligned base) before the first row and after the last; with ld > cols
+        the ld - cols elements between rows are guards too. data: copied in (an input; with inout an output that
+        starts at data); no data: an output full of NaN."""
+        ld = cols if ld is None else ld
+        pad = 256 // torch.empty((), dtype=dtype).element_size()
+        n = (rows - 1) * ld + cols if rows else 0
+        buf = self._new((pad + shift + n + pad,), dtype)
+        view = buf.as_strided((rows, cols), (ld, 1), pad + shift)
+        inside = torch.zeros(buf.shape, dtype=torch.bool, device=self.dev)
+        inside.as_strided((rows, cols), (ld, 1), pad + shift).fill_(True)
+        if data is not None:
+            view.copy_(data.reshape(rows, cols))
+        return self._add(name, buf, view, inside, data is None or inout)
 
     def o_t(self, name, rows, cols, dtype=BF):
         """[rows, cols] view of a [rows + 2, ld] buffer, ld = cols rounded up to 8, + 8."""
@@ -370,7 +390,7 @@ class Guards:
             same = after[out] == it["before"][out]
             assert bool(same.all()), f"{it['name']}: {int((~same).sum())} guard elements changed"
             if it["output"] or it["name"] in written:
-                if it["buf"].dtype != torch.uint8:
+                if it["buf"].dtype.is_floating_point:
                     bad = torch.isnan(it["view"])
                     assert not bool(bad.any()), f"{it['name']}: {int(bad.sum())} interior elements are NaN"
             else:

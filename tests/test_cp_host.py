@@ -96,6 +96,9 @@ def test_apply_context_parallel_reslices_built_model_rope(monkeypatch):
     S, n, r = 64, 4, 2
     monkeypatch.setenv("DEVICE", "cpu")
     monkeypatch.setenv("PICO_CP_ZIGZAG", "0")
+    # apply_context_parallel writes CONTEXT_PARALLEL=1 into os.environ: registered here so that it is put back, or
+    # every later model test of the same process (and the workers it spawns) takes the ring-attention path
+    monkeypatch.setenv("CONTEXT_PARALLEL", "0")
     monkeypatch.setattr(pgm, "process_group_manager",
                         SimpleNamespace(tp_world_size=1, dp_world_size=1, dp_rank=0, cp_world_size=n, cp_rank=r))
     cfg = LlamaConfig(hidden_size=128, intermediate_size=256, num_attention_heads=2, num_key_value_heads=2,

@@ -250,10 +250,16 @@ def test_rope_shapes_and_strides(B, S, NH, D):
     ref = H.rope_fused(x.cpu().double(), cos.double(), sin.double())
     assert rel_l2(out.cpu(), ref) < 4e-3
     assert max_abs(out.cpu(), ref) <= _ulp_bound(ref, 2)
-    # in-place aliasing (out == x)
+    # inplace=True rotates out of place and copies the result back: the kernel never sees out == x here
     y = x.clone()
     ops.apply_rotary_emb(y, cos.to(DEV)[:, : D // 2], sin.to(DEV)[:, : D // 2], inplace=True)
     assert torch.equal(y, out)
+    # the truly aliased launch (out == x, both the strided head slice), as the fused qkv path issues it
+    big2 = big.clone()
+    z = big2[:, :, 1:NH + 1]
+    ops._rope_launch(z, z, cos.to(DEV)[:, : D // 2], sin.to(DEV)[:, : D // 2], False)
+    assert torch.equal(z, out)
+    assert torch.equal(big2[:, :, 0], big[:, :, 0]) and torch.equal(big2[:, :, NH + 1], big[:, :, NH + 1])
 
 
 # ------------------------------------------------------------------------------------------ SwiGLU
