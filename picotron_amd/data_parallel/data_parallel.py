@@ -144,7 +144,8 @@ class DataParallelBucket(nn.Module):
             if param.requires_grad:
                 self.grad_accs.append(param.register_post_accumulate_grad_hook(
                     self._make_param_hook(param, self.bucket_manager)))
-                # fused path (ops.wgrad_accumulate): the wgrad GEMM accumulated into main_grad itself
+                # fused path: with main_grad, these two are the contract grad_sink.resolve reads (its "main"
+                # sink: the producer accumulated into main_grad itself, 1/W folded in, then calls ready())
                 param._pico_wgrad_sync = self._wgrad_sync
                 param._pico_wgrad_ready = self._make_ready_fn(param, self.bucket_manager)
 
@@ -153,8 +154,8 @@ class DataParallelBucket(nn.Module):
         world = bucket_manager.process_group_size
 
         def param_hook(*unused):
-            # A producer that accumulated into main_grad itself (fused wgrad GEMM, RMSNorm dw, embedding
-            # backward: ops.wgrad_accumulate / _norm_grad_target) hands autograd no gradient and records the
+            # A producer that accumulated into main_grad itself (any producer whose grad_sink.resolve said
+            # "main", or a deferred one: grad_sink.mark_produced) hands autograd no gradient and records the
             # param in this backward pass's fused set (ready()); AccumulateGrad still calls post-accumulate
             # hooks for a None gradient, and with persistent .grad buffers (HIP-graph replay, set_to_none=
             # False) param.grad is not None then, so the set — not the .grad — says there is nothing to add.

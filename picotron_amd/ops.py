@@ -23,7 +23,8 @@ import weakref
 import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook as _register_step_post_hook
 
-from . import _lib
+from . import _lib, grad_sink
+from .grad_sink import wgrad_fusion_enabled  # noqa: F401  (re-exported: used outside)
 
 _BF16 = torch.bfloat16
 
@@ -171,27 +172,21 @@ def _flush_norm_dw(dev):
 
 
 def _norm_grad_target(p, w):
-    """Where the norm-weight gradient goes (the micro-batch accumulation folded into the dw reduction,
-    as wgrad_accumulate does for the projections): (dw_mode, buffer, scale, ready-callback).
-    mode 2: DataParallelBucket's fp32 main_grad += dw (x 1/W on the syncing micro-batch), then the
-    bucket is told the parameter is ready; mode 1: bf16 .grad += dw in place (no DP wrapper, no hooks);
-    mode 0: a fresh dw handed to autograd (first micro-batch, hooks, fusion disabled)."""
-    if p is not None and wgrad_fusion_enabled() and p.is_contiguous():
-        mg = getattr(p, "main_grad", None)
-        if mg is not None and getattr(p, "_pico_wgrad_ready", None) is not None:
-            if mg.dtype == torch.float32 and mg.is_contiguous() and mg.shape == p.shape:
-                sync, world = p._pico_wgrad_sync()
-                if not sync and _norm_chain_enabled():
-                    # a non-syncing micro-batch: nothing waits for this bucket, so the dw reduction may be chained
-                    # into the next norm backward (its readiness call only records the parameter as produced by a
-                    # fused path, which must happen now, before its AccumulateGrad hook runs)
-                    p._pico_wgrad_ready()
-                    return 2, mg, 1.0, None
-                return 2, mg, (1.0 / world if sync else 1.0), p._pico_wgrad_ready
-        elif mg is None and not _has_hooks(p):
-            g = p.grad
-            if g is not None and g.dtype == p.dtype and g.is_contiguous() and g.shape == p.shape:
-                return 1, g, 1.0, None
+    """The norm weight's gradient sink (grad_sink.resolve) as the dw kernel's (dw_mode, buffer, scale,
+    ready-callback). mode 2: fp32 main_grad += dw (x scale), then the bucket is told the parameter is ready;
+    mode 1: bf16 .grad += dw in place; mode 0: a fresh dw handed to autograd (first micro-batch, hooks, fusion
+    disabled, a non-contiguous weight)."""
+    s = grad_sink.resolve(p, w.dtype) if p is not None and p.is_contiguous() else grad_sink.AUTOGRAD
+    if s.kind == "main":
+        if not p._pico_wgrad_sync()[0] and _norm_chain_enabled():
+            # a non-syncing micro-batch: nothing waits for this bucket, so the dw reduction may be chained
+            # into the next norm backward (its readiness call only records the parameter as produced by a
+            # fused path, which must happen now, before its AccumulateGrad hook runs)
+            s.ready()
+            return 2, s.buf, 1.0, None
+        return 2, s.buf, s.scale, s.ready
+    if s.kind == "grad":
+        return 1, s.buf, 1.0, None
     return 0, torch.empty_like(w), 1.0, None
 
 
@@ -347,16 +342,17 @@ def swiglu(gate, up):
 # The reference accumulates micro-batch gradients outside the GEMM: autograd's AccumulateGrad does
 # `p.grad += dW` in bf16 (DP = 1), and DataParallelBucket's hook does `main_grad += grad` in fp32
 # (ref picotron/data_parallel/data_parallel.py:131) — one extra sweep over every parameter per
-# micro-batch. Here the wgrad GEMM accumulates into the gradient's storage itself (hipBLASLt
-# epilogue, beta = 1): same sums, each rounded once instead of twice, no extra sweep.
-#   * DP bucket present (param.main_grad + param._pico_wgrad_ready, installed by DataParallelBucket):
-#     main_grad = beta * main_grad + alpha * dW in fp32 (out_dtype), alpha = beta = 1/W on the syncing
-#     micro-batch (the bucket's `grad_data /= W`, ref picotron/data_parallel/bucket.py:30, folded
-#     in), then the bucket is told the param is ready. One param per GEMM (bucket views of
-#     different params are not adjacent).
-#   * no DP wrapper, no grad hooks: the rows of one GEMM output are the .grad of its params (views of
-#     one buffer created on the first micro-batch); later micro-batches add into it with beta = 1.
-#   * anything else (hooks, foreign .grad tensors, non-bf16): plain dW handed to autograd.
+# micro-batch. Here every producer of a parameter gradient (the wgrad GEMMs below, the RMSNorm dw, the
+# embedding backward, the chunked LM-head CE) accumulates into the gradient's storage itself: same sums,
+# each rounded once instead of twice, no extra sweep. Where that storage is, is decided in one place,
+# grad_sink.resolve(p, grad_dtype) (the rule table is in grad_sink.py); first match wins:
+#   * p is None or PICO_WGRAD_FUSION=0                                   -> "autograd"
+#   * DP bucket (p.main_grad + p._pico_wgrad_ready, fp32 / contiguous / p's shape) -> "main":
+#     main_grad = scale * (main_grad + dW) in fp32, scale = 1/W on the syncing micro-batch (the bucket's
+#     `grad_data /= W`, ref picotron/data_parallel/bucket.py:30, folded in), then ready() tells the bucket
+#   * no DP wrapper, no grad hooks, gradient of p's dtype: no .grad yet   -> "fresh" (the output becomes .grad)
+#                                   a contiguous .grad of p's dtype/shape -> "grad" (added to in place)
+#   * anything else (hooks, foreign .grad tensors, another dtype)         -> "autograd": plain dW handed back
 # --------------------------------------------------------------------------------------------
 def _plain_grads(params, dW):
     out, r0 = [], 0
@@ -367,35 +363,20 @@ def _plain_grads(params, dW):
     return tuple(out)
 
 
-def _has_hooks(p):
-    hooks = getattr(p, "_post_accumulate_grad_hooks", None)
-    return bool(hooks) or bool(getattr(p, "_backward_hooks", None))
-
-
-def wgrad_fusion_enabled():
-    """PICO_WGRAD_FUSION=0 restores the reference's two-step accumulation (for bitwise tests)."""
-    return os.getenv("PICO_WGRAD_FUSION", "1") != "0"
-
-
 def wgrad_accumulate(params, dy2, x2):
     """dW = dy2^T x2 for row-stacked `params` ([sum rows, K]); returns the grads for autograd
     (None where the GEMM already accumulated into the parameter's gradient storage)."""
-    if not wgrad_fusion_enabled():
-        return _plain_grads(params, torch.mm(dy2.t(), x2))
-    if len(params) == 1 and getattr(params[0], "_pico_wgrad_ready", None) is not None \
-            and getattr(params[0], "main_grad", None) is not None:
-        p = params[0]
-        mg = p.main_grad
-        if mg.dtype == torch.float32 and mg.is_contiguous() and tuple(mg.shape) == tuple(p.shape):
-            sync, world = p._pico_wgrad_sync()
-            sc = 1.0 / world if sync else 1.0
-            torch.addmm(mg, dy2.t(), x2, beta=sc, alpha=sc, out_dtype=torch.float32, out=mg)
-            p._pico_wgrad_ready()
-            return (None,)
-    if len(params) > 1 and all(getattr(p, "_pico_wgrad_ready", None) is not None and
-                               getattr(p, "main_grad", None) is not None and p.main_grad.dtype == torch.float32 and
-                               p.main_grad.is_contiguous() and tuple(p.main_grad.shape) == tuple(p.shape) and
-                               p.dtype == dy2.dtype for p in params):
+    sinks = [grad_sink.resolve(p, dy2.dtype) for p in params]
+    kinds = {s.kind for s in sinks}
+    done = (None,) * len(params)
+    if kinds == {"main"} and len(params) == 1:
+        # one GEMM accumulates into the fp32 main_grad (one param per GEMM: bucket views of different params
+        # are not adjacent)
+        s = sinks[0]
+        torch.addmm(s.buf, dy2.t(), x2, beta=s.scale, alpha=s.scale, out_dtype=torch.float32, out=s.buf)
+        s.ready()
+        return done
+    if kinds == {"main"} and all(p.dtype == dy2.dtype for p in params):
         # Row-stacked parameters (q|k|v, gate|up) under DataParallelBucket: their main_grads sit in different
         # buckets (not one fp32 block), so one GEMM cannot accumulate into them. The reference's sequence — the
         # bf16 dW, then the bucket hook's main_grad += dW (x 1/W when syncing) — runs here, with the same kernels
@@ -408,47 +389,41 @@ def wgrad_accumulate(params, dy2, x2):
         from .data_parallel.bucket import get_kernels
         buf = torch.mm(dy2.t(), x2)
         r0 = 0
+        for p, s in zip(params, sinks):
+            n = p.shape[0]
+            get_kernels().accumulate(s.buf, buf[r0:r0 + n], round(1.0 / s.scale))  # divide by W when syncing
+            s.ready()
+            r0 += n
+        return done
+    if kinds == {"fresh"}:  # the rows of one GEMM output become the .grad of its params (views of one buffer)
+        buf = torch.mm(dy2.t(), x2)
+        r0 = 0
         for p in params:
             n = p.shape[0]
-            sync, world = p._pico_wgrad_sync()
-            get_kernels().accumulate(p.main_grad, buf[r0:r0 + n], world if sync else 1)
-            p._pico_wgrad_ready()
+            p.grad = buf[r0:r0 + n].view(p.shape)
             r0 += n
-        return (None,) * len(params)
-    if all(p.dtype == dy2.dtype and getattr(p, "main_grad", None) is None and not _has_hooks(p) for p in params):
-        grads = [p.grad for p in params]
-        if all(g is None for g in grads):
-            buf = torch.mm(dy2.t(), x2)
-            r0 = 0
-            for p in params:
-                n = p.shape[0]
-                p.grad = buf[r0:r0 + n].view(p.shape)
-                r0 += n
-            return (None,) * len(params)
-        if all(g is not None for g in grads):
-            base = grads[0]
-            nrows = sum(p.shape[0] for p in params)
-            K = params[0].shape[1]
-            ok = base.is_contiguous() and base.dtype == dy2.dtype
-            r0 = 0
-            sp = base.untyped_storage().data_ptr()
-            for p, g in zip(params, grads):
-                ok = ok and g.is_contiguous() and g.untyped_storage().data_ptr() == sp and \
-                    g.data_ptr() == base.data_ptr() + r0 * K * base.element_size()
-                r0 += p.shape[0]
-            if ok:
-                buf = torch.as_strided(base, (nrows, K), (K, 1))
-                torch.addmm(buf, dy2.t(), x2, out=buf)
-                return (None,) * len(params)
-            if all(g.dtype == dy2.dtype and g.shape == p.shape for p, g in zip(params, grads)):
-                # separately allocated gradients (a caller's own zeros_like per parameter): AccumulateGrad's in-place
-                # `grad += dW` done here (same values), not through autograd — see the DP branch above for why
-                buf = torch.mm(dy2.t(), x2)
-                r0 = 0
-                for p, g in zip(params, grads):
-                    g.add_(buf[r0:r0 + p.shape[0]].view(p.shape))
-                    r0 += p.shape[0]
-                return (None,) * len(params)
+        return done
+    if kinds == {"grad"}:
+        base = sinks[0].buf
+        K = params[0].shape[1]
+        sp = base.untyped_storage().data_ptr()
+        adjacent, r0 = True, 0
+        for p, s in zip(params, sinks):
+            adjacent = adjacent and s.buf.untyped_storage().data_ptr() == sp and \
+                s.buf.data_ptr() == base.data_ptr() + r0 * K * base.element_size()
+            r0 += p.shape[0]
+        if adjacent:  # the buffer a "fresh" micro-batch created: later micro-batches add into it with beta = 1
+            buf = torch.as_strided(base, (r0, K), (K, 1))
+            torch.addmm(buf, dy2.t(), x2, out=buf)
+            return done
+        # separately allocated gradients (a caller's own zeros_like per parameter): AccumulateGrad's in-place
+        # `grad += dW` done here (same values), not through autograd — see the DP branch above for why
+        buf = torch.mm(dy2.t(), x2)
+        r0 = 0
+        for p, s in zip(params, sinks):
+            s.buf.add_(buf[r0:r0 + p.shape[0]].view(p.shape))
+            r0 += p.shape[0]
+        return done
     return _plain_grads(params, torch.mm(dy2.t(), x2))
 
 
@@ -619,9 +594,7 @@ def _wgrad_paired(params, dy2, x2):
     plan = WP.plan(params[0], dy2, x2)
     if plan[0] == "skip":
         for p in params:
-            ready = getattr(p, "_pico_wgrad_ready", None)
-            if ready is not None and getattr(p, "main_grad", None) is not None:
-                ready()
+            grad_sink.mark_produced(p)
         return (None,) * len(params)
     return wgrad_accumulate(params, plan[1], plan[2])
 
@@ -683,19 +656,21 @@ class _EmbeddingFn(torch.autograd.Function):
     def backward(ctx, dy):
         (ids,) = ctx.saved_tensors
         w = ctx.w
-        if getattr(w, "_pico_wgrad_ready", None) is not None and getattr(w, "main_grad", None) is not None:
-            sync, world = w._pico_wgrad_sync()
-            _embedding_bwd_into(w.main_grad, ids, dy, 1.0)
-            if sync and world != 1:  # the bucket's grad_data /= W covers every row, touched or not
-                w.main_grad.mul_(1.0 / world)
-            w._pico_wgrad_ready()
+        s = grad_sink.resolve(w, dy.dtype)
+        if s.kind == "main":
+            _embedding_bwd_into(s.buf, ids, dy, 1.0)
+            if s.scale != 1.0:  # the bucket's grad_data /= W covers every row, touched or not
+                s.buf.mul_(s.scale)
+            s.ready()
             return None, None
-        if getattr(w, "main_grad", None) is None and not _has_hooks(w):
-            if w.grad is None:
-                w.grad = torch.zeros_like(w)
+        if s.kind == "grad":
+            _embedding_bwd_into(s.buf, ids, dy, 1.0)
+            return None, None
+        if s.kind == "fresh":
+            w.grad = torch.zeros_like(w)
             _embedding_bwd_into(w.grad, ids, dy, 1.0)
             return None, None
-        g = torch.zeros_like(w)
+        g = torch.zeros_like(w)  # "autograd": the dense gradient
         _embedding_bwd_into(g, ids, dy, 1.0)
         return None, g
 
@@ -877,19 +852,7 @@ class _LMHeadCEChunkedFn(torch.autograd.Function):
         xin = _wgrad_input(x2, V, x)  # x2, or x2^T's transposed view ("TT" wgrad form)
         need_w = ctx.needs_input_grad[1]
         # where dW goes (wgrad_accumulate's targets), decided once for the whole call
-        kind, dst, sc, ready = "autograd", None, 1.0, None
-        if need_w and wgrad_fusion_enabled():
-            mg = getattr(w, "main_grad", None)
-            if mg is not None and getattr(w, "_pico_wgrad_ready", None) is not None:
-                if mg.dtype == torch.float32 and mg.is_contiguous() and tuple(mg.shape) == tuple(w.shape):
-                    sync, world = w._pico_wgrad_sync()
-                    kind, dst, sc, ready = "main", mg, (1.0 / world if sync else 1.0), w._pico_wgrad_ready
-            elif mg is None and not _has_hooks(w) and w.dtype == x.dtype:
-                g = w.grad
-                if g is None:
-                    kind = "fresh"
-                elif g.is_contiguous() and g.dtype == w.dtype and tuple(g.shape) == tuple(w.shape):
-                    kind, dst = "grad", g
+        kind, dst, sc, ready = grad_sink.resolve(w, x.dtype) if need_w else grad_sink.AUTOGRAD
         lib = _lib.load()
         conc = "lm" in _conc_tags() and not _NO_SIDE[0]
         # grouped weight gradient (wgrad_pair's groups, one chunk per micro-batch): the logits / dlogits go into the
@@ -932,14 +895,12 @@ class _LMHeadCEChunkedFn(torch.autograd.Function):
                     if kind == "main":  # fp32 main_grad: 1/W folds into the first chunk's beta and every alpha
                         torch.addmm(dst, lg.t(), xc, beta=(sc if c0 == 0 else 1.0), alpha=sc, out_dtype=torch.float32,
                                     out=dst)
-                    elif kind in ("grad", "fresh_acc", "autograd_acc"):
+                    elif dst is not None:  # "grad", and the later chunks of "fresh" / "autograd"
                         torch.addmm(dst, lg.t(), xc, out=dst)
-                    elif kind == "fresh":
-                        w.grad = dst = torch.mm(lg.t(), xc)
-                        kind = "fresh_acc"
-                    else:  # "autograd": a buffer handed back from the backward
+                    else:  # first chunk: the new .grad ("fresh"), or a buffer handed back from the backward
                         dst = torch.mm(lg.t(), xc)
-                        kind = "autograd_acc"
+                        if kind == "fresh":
+                            w.grad = dst
             if ctx.needs_input_grad[0]:
                 if wt is not None:
                     torch.mm(lg, wt.t(), out=dx[c0:c1])
@@ -955,7 +916,7 @@ class _LMHeadCEChunkedFn(torch.autograd.Function):
                    "pico_ce_mean")
         ctx.save_for_backward(dx)
         ctx.xshape = x.shape
-        ctx.dw = dst if kind == "autograd_acc" else None
+        ctx.dw = dst if kind == "autograd" else None
         ctx.ready = ready
         return loss
 
