@@ -242,7 +242,8 @@ int pico_attn_bwd(const pico_attn_args* args, void* stream);
  * or slices of them, ref :183-186) and the ring's internal [B, S, H, D] one use the same entry point:
  * out fp32, strides (batch, seq, head), unit head_dim stride; lse fp32, strides (batch, head, seq);
  * block_out bf16 (block_out_f32 == 0) or fp32, strides (batch, seq, head), unit head_dim stride;
- * block_lse fp32, strides (batch, head, seq). out and block_out rows 16-byte aligned. */
+ * block_lse fp32, strides (batch, head, seq). out and block_out rows 16-byte aligned. head_dim: any multiple
+ * of 8 up to 256; batch * seqlen < 2^31. */
 int pico_attn_merge(float* out, const int64_t* out_strides, float* lse, const int64_t* lse_strides,
                     const void* block_out, const int64_t* block_out_strides, int block_out_f32,
                     const float* block_lse, const int64_t* block_lse_strides, int64_t batch, int64_t seqlen,

@@ -111,7 +111,10 @@ def update_out_and_lse(out, lse, block_out, block_lse, slice_=None):
         `_update` rebinding does (one fp32 copy each; the ring itself merges in place through _merge_bshd).
     Operands of other dtypes are cast as the reference does (block_out.to(fp32) when it is neither bf16 — read
     natively by the kernel — nor fp32; block_lse and a non-slice running out / lse to fp32). Runs on
-    pico_attn_merge through element strides."""
+    pico_attn_merge through element strides; any head dim that is a multiple of 8, up to 256.
+    A block with block_lse = -inf (no visible key) and finite block_out leaves the running row as it is, bit for
+    bit. A running lse of -inf gives a NaN lse, as the reference's formula does (lse - logsigmoid(lse - block_lse)
+    is -inf - (-inf)): the ring never produces one, its first block of a row always holds the diagonal."""
     if block_out.dim() != 4 or block_lse.dim() != 3 or tuple(block_lse.shape) != tuple(block_out.shape[:3]):
         raise ValueError("update_out_and_lse: block_out must be [B, H, S, D] and block_lse [B, H, S]")
     if block_out.dtype not in (torch.bfloat16, torch.float32):

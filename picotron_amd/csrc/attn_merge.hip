@@ -6,7 +6,9 @@
 // [B, H, S, D] fp32, lse [B, H, S, 1], possibly sliced views, ref :183-186) and the ring's internal one
 // (out [B, S, H, D]): out fp32 (strides b, s, h; unit d), lse fp32 (strides b, h, s), block_out bf16 or fp32
 // (strides b, s, h; unit d), block_lse fp32 (strides b, h, s). D/8 lanes per (b, s, h) row, 8 elements each
-// (HBM-bound: 4+4+2 B per element, plus 12 B per row).
+// (HBM-bound: 4+4+2 B per element, plus 12 B per row). Every lane of a row reads the running lse before the lane of
+// columns 0..7 overwrites it, so a row's lanes always share a wave: the lane mapping is attn_merge_plan.h's.
+#include "attn_merge_plan.h"
 #include "common.h"
 
 namespace {
@@ -16,15 +18,14 @@ struct MergeStrides {
 };
 
 template <bool BO_F32>
-__global__ __launch_bounds__(256) void attn_merge_kernel(float* __restrict__ out, float* __restrict__ lse,
-                                                         const void* __restrict__ bo_, const float* __restrict__ blse,
-                                                         int B, int S, int H, int D, MergeStrides st, int first) {
-  const int lpr = D / 8;
-  const int64_t rows = (int64_t)B * S * H;
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = gid / lpr;
-  const int sub = (int)(gid % lpr);
-  if (row >= rows) return;
+__global__ __launch_bounds__(MERGE_THREADS) void attn_merge_kernel(float* __restrict__ out, float* __restrict__ lse,
+                                                                   const void* __restrict__ bo_,
+                                                                   const float* __restrict__ blse, int B, int S, int H,
+                                                                   int lpr, int shift, MergeStrides st, int first) {
+  const MergeLane ml = merge_lane(lpr, shift, blockIdx.x, threadIdx.x, (int64_t)B * S * H);
+  if (!ml.live) return;
+  const int64_t row = ml.row;
+  const int sub = ml.sub;
   const int h = (int)(row % H);
   const int64_t bsr = row / H;
   const int s = (int)(bsr % S);
@@ -78,14 +79,19 @@ extern "C" int pico_attn_merge(float* out, const int64_t* out_strides, float* ls
                                int64_t heads, int64_t head_dim, int first, void* stream) {
   PICO_REQUIRE(out && lse && block_out && block_lse, "pico_attn_merge: null pointer");
   PICO_REQUIRE(out_strides && lse_strides && block_out_strides && block_lse_strides, "pico_attn_merge: null strides");
-  PICO_REQUIRE(head_dim % 8 == 0 && head_dim <= 256, "pico_attn_merge: bad head_dim");
+  PICO_REQUIRE(merge_dim_ok(head_dim), "pico_attn_merge: bad head_dim");
+  PICO_REQUIRE(batch >= 0 && seqlen >= 0 && heads >= 0 && batch <= 0x7fffffff && seqlen <= 0x7fffffff &&
+                   heads <= 0x7fffffff && batch * seqlen <= 0x7fffffff,
+               "pico_attn_merge: bad batch / seqlen / heads");
   for (int d = 0; d < 3; ++d) {
     PICO_REQUIRE(block_out_strides[d] % (block_out_f32 ? 4 : 8) == 0 && out_strides[d] % 4 == 0,
                  "pico_attn_merge: out / block_out strides must keep 16-byte alignment");
   }
   PICO_REQUIRE(((uintptr_t)out | (uintptr_t)block_out) % 16 == 0, "pico_attn_merge: out / block_out must be 16-byte aligned");
-  const int64_t threads = batch * seqlen * heads * (head_dim / 8);
-  if (threads == 0) return 0;
+  const int64_t rows = batch * seqlen * heads;
+  if (rows == 0) return 0;
+  const MergePlan p = merge_plan(rows, head_dim);
+  PICO_REQUIRE(p.grid <= 0x7fffffff, "pico_attn_merge: too many rows");
   MergeStrides st;
   for (int d = 0; d < 3; ++d) {
     st.o[d] = out_strides[d];
@@ -95,11 +101,13 @@ extern "C" int pico_attn_merge(float* out, const int64_t* out_strides, float* ls
   }
   hipStream_t s = (hipStream_t)stream;
   if (block_out_f32) {
-    PICO_TRY(pico_launch(PICO_K_ATTN_MERGE, "attn_merge", attn_merge_kernel<true>, dim3(pico_cdiv(threads, 256)), dim3(256), 0,
-                         s, out, lse, block_out, block_lse, (int)batch, (int)seqlen, (int)heads, (int)head_dim, st, first));
+    PICO_TRY(pico_launch(PICO_K_ATTN_MERGE, "attn_merge", attn_merge_kernel<true>, dim3((unsigned)p.grid),
+                         dim3(MERGE_THREADS), 0, s, out, lse, block_out, block_lse, (int)batch, (int)seqlen, (int)heads,
+                         p.lpr, p.shift, st, first));
   } else {
-    PICO_TRY(pico_launch(PICO_K_ATTN_MERGE, "attn_merge", attn_merge_kernel<false>, dim3(pico_cdiv(threads, 256)), dim3(256), 0,
-                         s, out, lse, block_out, block_lse, (int)batch, (int)seqlen, (int)heads, (int)head_dim, st, first));
+    PICO_TRY(pico_launch(PICO_K_ATTN_MERGE, "attn_merge", attn_merge_kernel<false>, dim3((unsigned)p.grid),
+                         dim3(MERGE_THREADS), 0, s, out, lse, block_out, block_lse, (int)batch, (int)seqlen, (int)heads,
+                         p.lpr, p.shift, st, first));
   }
   return 0;
 }

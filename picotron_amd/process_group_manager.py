@@ -5,6 +5,7 @@ picotron/process_group_manager.py:5-68: a module-global `process_group_manager` 
 The grid is laid out [dp][pp][cp][tp] (tp fastest), as in ref :13; the DP gradient buckets reduce
 over `cp_dp_group` (ref :22), which on MI355X is an RCCL communicator over xGMI.
 """
+import atexit
 import os
 
 import torch
@@ -73,6 +74,20 @@ def setup_process_group_manager(tp_size, cp_size, pp_size, dp_size):
     global process_group_manager
     process_group_manager = ProcessGroupManager(tp_size, cp_size, pp_size, dp_size)
     return process_group_manager
+
+
+def _release_at_exit():
+    """The manager holds the world group and every subgroup, so after dist.destroy_process_group() the backend
+    objects and their worker threads live on until the interpreter clears this module, i.e. into finalization. A
+    gloo worker thread that then drops its last reference to a finished collective's tensors asks for the GIL, is
+    ended by the finalizing interpreter in the middle of a C++ frame, and the process aborts ("terminate called
+    without an active exception", a few percent of the exits of a gloo rank). atexit handlers run before
+    finalization starts: letting go here ends the threads while the interpreter is still whole."""
+    global process_group_manager
+    process_group_manager = None
+
+
+atexit.register(_release_at_exit)
 
 
 def tp_world_size():

@@ -53,7 +53,7 @@ def _staged_comm_class(base):
     return HostStagedCommunicate
 
 
-def _worker(rank, world, port, causal, zigzag=False, S=1024, B=2, Hq=4, rope=False):
+def _worker(rank, world, port, causal, zigzag=False, S=1024, B=2, Hq=4, rope=False, D=64, Hkv=None):
     import sys
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -68,9 +68,9 @@ def _worker(rank, world, port, causal, zigzag=False, S=1024, B=2, Hq=4, rope=Fal
     CP.ContextCommunicate = _staged_comm_class(CP.ContextCommunicate)
 
     dev = "cuda:0"
-    D = 64
+    Hkv = Hq if Hkv is None else Hkv  # fewer kv heads: native GQA, k / v travel the ring with Hkv heads
     g = torch.Generator(device="cpu").manual_seed(21)  # identical full tensors on every rank
-    q, k, v, do = [torch.randn(B, S, Hq, D, generator=g).to(BF).to(dev) for _ in range(4)]
+    q, k, v, do = [torch.randn(B, S, h, D, generator=g).to(BF).to(dev) for h in (Hq, Hkv, Hkv, Hq)]
     scale = D ** -0.5
     # rope: q and k rotated before attention with the whole-sequence tables, and on each rank with the tables
     # update_rope_for_context_parallel slices for it (ref picotron/context_parallel/context_parallel.py:189-195,
@@ -110,7 +110,8 @@ def _worker(rank, world, port, causal, zigzag=False, S=1024, B=2, Hq=4, rope=Fal
     dist.barrier()
     dist.destroy_process_group()
     if bad:
-        raise AssertionError(f"rank {rank} cp={world} causal={causal} zigzag={zigzag}: {bad} (all: {errs})")
+        raise AssertionError(f"rank {rank} cp={world} causal={causal} zigzag={zigzag} Hq={Hq} Hkv={Hkv} D={D}: {bad} "
+                             f"(all: {errs})")
 
 
 @pytest.mark.parametrize("world,causal,zigzag,S,B,Hq,rope", [
@@ -126,4 +127,12 @@ def test_ring_attention_multi_rank(world, causal, zigzag, S, B, Hq, rope):
     rank holds. cp = 8 (C5's ring size): the 8-step ring loop, and the zig-zag split
     into 2 cp = 16 chunks, at S = 2048 and at C5's own S = 32768."""
     mp.start_processes(_worker, args=(world, _free_port(), causal, zigzag, S, B, Hq, rope), nprocs=world, join=True,
+                       start_method="spawn")
+
+
+@pytest.mark.parametrize("zigzag,Hq,Hkv,D", [(True, 4, 2, 64), (False, 2, 1, 128)])
+def test_ring_attention_multi_rank_gqa_and_d128(zigzag, Hq, Hkv, D):
+    """What ring_attention advertises beside the reference's shapes: native GQA (k / v with Hkv < Hq heads on the
+    ring, dK / dV summed over the group) and D = 128, forward and backward across two ranks; same tolerances."""
+    mp.start_processes(_worker, args=(2, _free_port(), True, zigzag, 512, 2, Hq, False, D, Hkv), nprocs=2, join=True,
                        start_method="spawn")
