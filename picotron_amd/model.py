@@ -25,6 +25,7 @@ import torch.nn.functional as F
 from . import ops
 from . import wgrad_pair as WP
 from . import process_group_manager as pgm
+from .wgrad_operands import Proj
 
 
 @dataclass
@@ -145,8 +146,8 @@ class RMSNorm(nn.Module):
     def forward(self, hidden_states, residual=None, dropout_p=0.0, prenorm=False, residual_in_fp32=False,
                 return_dropout_mask=False, _pair=None):
         # the norm outputs of this model feed projections (qkv, gate|up, LM head) whose weight-gradient
-        # GEMM reads y^T: the kernel writes it alongside y (ops._wgrad_input picks it up). _pair: paired
-        # weight-gradient hints (wgrad_pair; DecoderLayer._pair_hints)
+        # GEMM reads y^T: the kernel writes it alongside y (wgrad_operands.saved_input picks it up). _pair: the
+        # (reader, writer) projections of y and of the norm's input (wgrad_operands; DecoderLayer._pair_hints)
         return ops.layer_norm_fn(hidden_states, self.weight, None, residual=residual, eps=self.eps,
                                  dropout_p=dropout_p, prenorm=prenorm, residual_in_fp32=residual_in_fp32,
                                  is_rms_norm=True, return_dropout_mask=return_dropout_mask, _emit_transposed=True,
@@ -274,36 +275,30 @@ class DecoderLayer(nn.Module):
         return x
 
     def _pair_hints(self):
-        """Paired weight-gradient hints (wgrad_pair) of this layer's four projections, (weight, N, K) each — the
-        weight keys its pair buffers — or None when the pairing is off or a projection is not a plain bias-free
-        nn.Linear on the fused paths (TP / CP layers, PICO_UNFUSED)."""
+        """This layer's four projections as wgrad_operands.Proj (paired weight gradients: the weight keys its group
+        buffers), or None when the pairing is off or a projection is not a plain bias-free nn.Linear on the fused
+        paths (TP / CP layers, PICO_UNFUSED)."""
         if not WP.active() or os.getenv("PICO_UNFUSED", "0") == "1" or os.getenv("CONTEXT_PARALLEL", "0") == "1":
             return None
         a, m = self.attention, self.mlp
         lins = (a.q_proj, a.k_proj, a.v_proj, a.out_proj, m.gate_proj, m.up_proj, m.down_proj)
         if any(type(t) is not nn.Linear or t.bias is not None for t in lins) or pgm.tp_world_size() > 1:
             return None
-        hd, inter = a.out_proj.weight.shape[0], m.down_proj.weight.shape[1]
-        nqkv = a.q_proj.weight.shape[0] + a.k_proj.weight.shape[0] + a.v_proj.weight.shape[0]
-        return {"qkv": (a.q_proj.weight, nqkv, a.q_proj.weight.shape[1]),
-                "out": (a.out_proj.weight, hd, a.out_proj.weight.shape[1]),
-                "gu": (m.gate_proj.weight, 2 * m.gate_proj.weight.shape[0], m.gate_proj.weight.shape[1]),
-                "down": (m.down_proj.weight, hd, inter)}
+        return {"qkv": Proj.of(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight), "out": Proj.of(a.out_proj.weight),
+                "gu": Proj.of(m.gate_proj.weight, m.up_proj.weight), "down": Proj.of(m.down_proj.weight)}
 
-    def forward_fused(self, delta, residual, prev_down=None):
+    def forward_fused(self, delta, residual, prev_down=None, hints=None):
         """Same layer with the residual adds fused into the norms (layer_norm_fn prenorm form):
         the layer input is residual + delta (residual None for the first layer). Returns the
         (delta, residual) pair whose sum is this layer's output; every sum is rounded to bf16 exactly
-        like the reference's `x + f(x)`. prev_down: the previous layer's down-projection pair hint (delta is its
-        output, so the input norm's dx is that projection's dy)."""
-        hints = self._pair_hints()
+        like the reference's `x + f(x)`. prev_down: the previous layer's down projection (delta is its output, so
+        the input norm's dx is that projection's dy). hints: this layer's _pair_hints() when the caller has them."""
+        hints = hints or self._pair_hints()
         p_in = (hints["qkv"], prev_down) if hints else None
         p_post = (hints["gu"], hints["out"]) if hints else None
-        if residual is None:  # prenorm form without a residual: x is the norm's second output, so the
-            # embedding output has one consumer and its gradient needs no separate add
-            h_in, x = self.input_layernorm(delta, residual=None, prenorm=True, _pair=p_in)
-        else:
-            h_in, x = self.input_layernorm(delta, residual=residual, prenorm=True, _pair=p_in)
+        # (first layer: the prenorm form without a residual, x is the norm's second output, so the embedding output
+        # has one consumer and its gradient needs no separate add)
+        h_in, x = self.input_layernorm(delta, residual=residual, prenorm=True, _pair=p_in)
         attn = self.attention(h_in, self.cos, self.sin, out_hint=hints["out"] if hints else None)
         h2, x = self.post_attention_layernorm(attn, residual=x, prenorm=True, _pair=p_post)
         return self.mlp(h2, down_hint=hints["down"] if hints else None), x
@@ -372,19 +367,18 @@ class Llama(nn.Module):
                 x = layer(x)
             return self.final_proj(self.final_norm(x))
         delta, residual = x, None
-        down = None  # the previous layer's down-projection pair hint (wgrad_pair)
-        for b, layer in enumerate(self.decoder_layers):
-            delta, residual = layer.forward_fused(delta, residual, prev_down=down)
+        down = None  # the previous layer's down projection (wgrad_operands.Proj)
+        for layer in self.decoder_layers:
             hints = layer._pair_hints()
+            delta, residual = layer.forward_fused(delta, residual, prev_down=down, hints=hints)
             down = hints["down"] if hints else None
         # the fused LM head + CE (return_hidden) groups its weight gradient too: the final norm's y^T goes into the
-        # head's x^T group slot (wgrad_pair)
+        # head's x^T group slot
         head = getattr(self, "final_proj", None)
-        lm = (head.weight, head.weight.shape[0], head.weight.shape[1]) if (
+        lm = Proj.of(head.weight) if (
             return_hidden and down is not None and type(head) is nn.Linear and head.bias is None) else None
         pair = (lm, down) if down is not None else None
-        h = self.final_norm(delta, _pair=pair) if residual is None else \
-            self.final_norm(delta, residual=residual, _pair=pair)
+        h = self.final_norm(delta, residual=residual, _pair=pair)
         if return_hidden:
             return h
         return _proj(self.final_proj, h)

@@ -24,6 +24,8 @@ import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook as _register_step_post_hook
 
 from . import _lib, grad_sink
+from . import wgrad_operands as WO
+from . import wgrad_pair as WP
 from .grad_sink import wgrad_fusion_enabled  # noqa: F401  (re-exported: used outside)
 
 _BF16 = torch.bfloat16
@@ -52,9 +54,8 @@ def _aligned16(t):
 class _RMSNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, eps, prenorm, want_t=False, pair=None):
-        """pair: (xt_for, dy_for) paired-wgrad hints (wgrad_pair): the (weight, N, K) of the projection that reads
-        y (its x^T goes into that projection's pair buffer) and of the projection whose output is x (dx goes into
-        its dy pair buffer), or None."""
+        """pair: (reader, writer) or None (wgrad_operands.Proj each, or None): the projection that reads y (y^T goes
+        into its x^T group slot) and the projection whose output is x (dx goes into its dy group slot)."""
         _need(x, "x")
         _need(weight, "weight")
         # a chained dw left pending while no backward pass runs means the pass that created it raised before its
@@ -76,14 +77,11 @@ class _RMSNormFn(torch.autograd.Function):
             res2 = _aligned16(residual.reshape(-1, cols).contiguous())
             res_out = torch.empty_like(x2)
         w = _aligned16(weight.contiguous())
-        yt = None
-        if want_t and os.getenv("PICO_XT_WGRAD", "1") != "0" and cols in (1024, 2048) and rows % 32 == 0:
-            # (x2, res2 and w are 16-byte aligned: _aligned16 above)
-            # y^T as a by-product for the next projection's TT wgrad GEMM (no separate transpose pass), into the
-            # projection's x^T pair buffer when its weight gradients are paired
-            yt = _pair_xt(pair[0] if pair else None, cols, rows, x) if pair else None
-            if yt is None:
-                yt = torch.empty((cols, rows), dtype=x.dtype, device=x.device)
+        # y^T as a by-product for the next projection's TT wgrad GEMM (no separate transpose pass)
+        # (x2, res2 and w are 16-byte aligned: _aligned16 above)
+        yt = WO.xt_sink(pair[0] if pair else None, cols, rows, x,
+                        eligible=want_t and cols in (1024, 2048) and rows % 32 == 0)
+        if yt is not None:
             _lib.check(lib.pico_rmsnorm_fwd_t(_lib.ptr(x2), _lib.ptr(res2), _lib.ptr(w), _lib.ptr(y), _lib.ptr(res_out),
                                               _lib.ptr(rstd), _lib.ptr(yt), yt.stride(0), rows, cols, float(eps),
                                               _lib.stream_of(x)), "pico_rmsnorm_fwd_t")
@@ -98,9 +96,7 @@ class _RMSNormFn(torch.autograd.Function):
         ctx.has_residual = residual is not None
         ctx.prenorm = prenorm
         ctx.pair_dy = pair[1] if pair else None
-        y = y.view(shape)
-        if yt is not None:
-            y._pico_t = yt
+        y = WO.attach_t(y.view(shape), yt)
         if prenorm:
             return y, (res_out if res_out is not None else x2).view(shape)
         return y
@@ -115,7 +111,7 @@ class _RMSNormFn(torch.autograd.Function):
         if ctx.prenorm and rest and rest[0] is not None:
             dres = _aligned16(rest[0].reshape(-1, cols).contiguous())
         lib = _lib.load()
-        dx = _pair_dy(ctx.pair_dy, rows, cols, x_eff)  # the producing projection's dy pair buffer (wgrad_pair)
+        dx = WO.dy_sink_of_output(ctx.pair_dy, rows, cols, x_eff)  # the dy group slot of the projection before
         if dx is None:
             dx = torch.empty_like(x_eff)
         mode, target, scale, ready = _norm_grad_target(ctx.weight_param, w)
@@ -188,31 +184,6 @@ def _norm_grad_target(p, w):
     if s.kind == "grad":
         return 1, s.buf, 1.0, None
     return 0, torch.empty_like(w), 1.0, None
-
-
-def _pair_xt(hint, K, T, like):
-    """The [K, T] x^T pair-buffer slot (row stride 2T) of the projection `hint` = (weight, N, K') for the current
-    micro-batch, or None (pairing off, or a shape that does not match)."""
-    if hint is None:
-        return None
-    from . import wgrad_pair as WP
-    w, N, Kh = hint
-    if Kh != K or T % 8 != 0:
-        return None
-    return WP.xt_out(w, N, K, T, like.dtype, like.device)
-
-
-def _pair_dy(hint, T, N, like):
-    """The [T, N] dy pair-buffer slot of the projection `hint` = (weight, N', K) for the current micro-batch, or None."""
-    if hint is None:
-        return None
-    from . import wgrad_pair as WP
-    w, Nh, K = hint
-    if Nh != N:
-        return None
-    # only into buffers the projection's forward created (its x^T went to the pair buffer): a path whose x^T was
-    # never paired (PICO_SWIGLU_T=0, T % 64 != 0, an attention without O^T) gets no pair buffers from here
-    return WP.dy_out_existing(w, N, K, T, like.dtype, like.device)
 
 
 def rms_norm(x, weight, eps=1e-5, residual=None, prenorm=False):
@@ -518,20 +489,6 @@ def transpose_2d(x, out=None):
     return out
 
 
-def _wgrad_input(x2, n_out, x=None):
-    """What the backward keeps of a projection's input x2 [T, K] for its wgrad: x2 itself, or x2^T as a
-    transposed view of a contiguous [K, T] copy where hipBLASLt's "TT" wgrad form saves more than the
-    transpose costs (output width >= 3 K: qkv, gate|up, LM head; gemm_layout_probe.py --wgrad)."""
-    if os.getenv("PICO_XT_WGRAD", "1") == "0" or not x2.is_cuda:
-        return x2
-    xt = getattr(x, "_pico_t", None)  # a producer wrote x^T as a by-product (attention output)
-    if xt is not None and tuple(xt.shape) == (x2.shape[1], x2.shape[0]):
-        return xt.t()
-    if n_out >= 3 * x2.shape[1]:
-        return transpose_2d(x2).t()
-    return x2
-
-
 def refresh_weight_transposes():
     _wt_purge()
     for ent in list(_WT_CACHE.values()):
@@ -590,7 +547,6 @@ def _wgrad_paired(params, dy2, x2):
     """wgrad_accumulate with paired weight gradients (wgrad_pair): the first micro-batch of a pair whose operands
     sit in the pair buffers defers its GEMM (a DP readiness callback still marks the parameter as produced by a
     fused path, so the bucket hook does not add a stale .grad); the second runs one GEMM over both."""
-    from . import wgrad_pair as WP
     plan = WP.plan(params[0], dy2, x2)
     if plan[0] == "skip":
         for p in params:
@@ -745,7 +701,7 @@ class _LMHeadCEFn(torch.autograd.Function):
                                                            int(ignore_index), _lib.stream_of(x)),
                    "pico_cross_entropy_fwd_grad")
         loss = loss_rows.sum() / n_valid
-        ctx.save_for_backward(logits, _wgrad_input(x2, V, x), w)
+        ctx.save_for_backward(logits, WO.saved_input(x2, V, x), w)
         ctx.xshape = x.shape
         return loss.to(x.dtype)
 
@@ -849,7 +805,7 @@ class _LMHeadCEChunkedFn(torch.autograd.Function):
         chunk = max(1, min(int(chunk), T))
         buf = None
         wt = weight_t(w, (w,)) if wt_dgrad_enabled() else None
-        xin = _wgrad_input(x2, V, x)  # x2, or x2^T's transposed view ("TT" wgrad form)
+        xin = WO.saved_input(x2, V, x)  # x2, or x2^T's transposed view ("TT" wgrad form)
         need_w = ctx.needs_input_grad[1]
         # where dW goes (wgrad_accumulate's targets), decided once for the whole call
         kind, dst, sc, ready = grad_sink.resolve(w, x.dtype) if need_w else grad_sink.AUTOGRAD
@@ -858,12 +814,11 @@ class _LMHeadCEChunkedFn(torch.autograd.Function):
         # grouped weight gradient (wgrad_pair's groups, one chunk per micro-batch): the logits / dlogits go into the
         # weight's dy group slot and x^T sits in its x^T slot (the final norm writes it there), and the dW GEMM runs
         # once per group, over K = r T, in the group's last micro-batch (PICO_LM_WGRAD_GROUP=0: per micro-batch)
-        from . import wgrad_pair as WP
         grouped = (need_w and chunk >= T and kind in ("main", "grad") and WP.active()
                    and os.getenv("PICO_LM_WGRAD_GROUP", "1") != "0")
         if grouped:  # only when the final norm put this micro-batch's x^T into the head's group slot:
             # otherwise plan() runs a GEMM per micro-batch and a [G T, V] group buffer would be dead weight
-            buf = WP.dy_out_if_paired(w, xin, V, H, T, x.dtype, x.device)
+            buf = WO.dy_sink_of_input(w, xin, V, H, T, x)
         if buf is None:
             buf = torch.empty(chunk, V, dtype=x.dtype, device=x.device)
         for c0 in range(0, T, chunk):
@@ -1071,7 +1026,7 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w):
         x2 = x.reshape(-1, x.shape[-1])
-        ctx.save_for_backward(_wgrad_input(x2, w.shape[0], x) if ctx.needs_input_grad[1] else x2, w)
+        ctx.save_for_backward(WO.saved_input(x2, w.shape[0], x) if ctx.needs_input_grad[1] else x2, w)
         ctx.xshape = x.shape
         return torch.nn.functional.linear(x, w)
 
@@ -1128,7 +1083,7 @@ class _GateUpSwiGLUFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_gate, w_up, down_hint=None):
-        """down_hint: (weight, N, K) of the down projection reading h (wgrad_pair: h^T into its x^T pair buffer)."""
+        """down_hint: the down projection reading h (wgrad_operands.Proj: h^T into its x^T group slot), or None."""
         _need(x, "x")
         I = w_gate.shape[0]
         W = stacked_weight((w_gate, w_up))
@@ -1136,24 +1091,18 @@ class _GateUpSwiGLUFn(torch.autograd.Function):
         gu = torch.matmul(x2, W.t())  # [T, 2I]
         T = gu.shape[0]
         h = torch.empty((T, I), dtype=x.dtype, device=x.device)
-        ht = None
-        if os.getenv("PICO_XT_WGRAD", "1") != "0" and os.getenv("PICO_SWIGLU_T", "1") != "0" and T % 64 == 0 \
-                and I % 64 == 0 and gu.data_ptr() % 16 == 0:
-            # h^T as a by-product (the down projection's wgrad reads it in the TT GEMM form)
-            ht = _pair_xt(down_hint, I, T, x)
-            if ht is None:
-                ht = torch.empty((I, T), dtype=x.dtype, device=x.device)
+        # h^T as a by-product (the down projection's wgrad reads it in the TT GEMM form)
+        ht = WO.xt_sink(down_hint, I, T, x, eligible=os.getenv("PICO_SWIGLU_T", "1") != "0" and T % 64 == 0
+                        and I % 64 == 0 and gu.data_ptr() % 16 == 0)
+        if ht is not None:
             _lib.check(_lib.load().pico_swiglu_fwd_t(_lib.ptr(gu), _lib.ptr(gu[:, I:]), _lib.ptr(h), _lib.ptr(ht), T, I,
                                                      2 * I, I, ht.stride(0), _lib.stream_of(gu)), "pico_swiglu_fwd_t")
         else:
             _swiglu_fwd(gu, gu[:, I:], h, T, I, 2 * I, I)
-        ctx.save_for_backward(_wgrad_input(x2, 2 * I, x), gu, W)
+        ctx.save_for_backward(WO.saved_input(x2, 2 * I, x), gu, W)
         ctx.params = (w_gate, w_up)
         ctx.xshape = x.shape
-        out = h.view(*x.shape[:-1], I)
-        if ht is not None:
-            out._pico_t = ht
-        return out
+        return WO.attach_t(h.view(*x.shape[:-1], I), ht)
 
     @staticmethod
     def backward(ctx, dh):
@@ -1162,8 +1111,7 @@ class _GateUpSwiGLUFn(torch.autograd.Function):
         d = dh.reshape(-1, I)
         if not d.is_contiguous():
             d = d.contiguous()
-        from . import wgrad_pair as WP
-        dgu = WP.dy_out_if_paired(ctx.params[0], x2, 2 * I, x2.shape[1], gu.shape[0], gu.dtype, gu.device)
+        dgu = WO.dy_sink_of_input(ctx.params[0], x2, 2 * I, x2.shape[1], gu.shape[0], gu)
         if dgu is None:
             dgu = torch.empty_like(gu)
         _swiglu_bwd(d, gu, gu[:, I:], dgu, dgu[:, I:], gu.shape[0], I, 2 * I, I)
@@ -1213,7 +1161,8 @@ def _check_qkv(q, k, v):
 # Packed rows: several documents share one row of the batch. doc_start[b, i] is the index of the first token of the
 # document that holds token i (non-decreasing along the row, doc_start[b, 0] == 0, doc_start[b, i] <= i); under a
 # document mask query i sees key j iff doc_start[b, i] <= j <= i. The helpers below are plain torch and work on any
-# device; they describe the mask, no kernel here applies it yet.
+# device; they only describe the mask: no attention kernel takes document bounds (_lib.AttnArgs has no field for
+# them), so nothing in this package applies it.
 def doc_starts_from_eos(input_ids, eos_token_id):
     """doc_start int32 [B, S] of packed rows: a token that follows an EOS opens a new document, and token 0
     always does (the EOS itself is the last token of its document)."""
@@ -1383,7 +1332,7 @@ class _QKVRopeAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wq, wk, wv, cos, sin, nh, nkv, causal, out_hint=None):
-        """out_hint: (weight, N, K) of the out-projection reading O (wgrad_pair: O^T into its x^T pair buffer)."""
+        """out_hint: the out-projection reading O (wgrad_operands.Proj: O^T into its x^T group slot), or None."""
         _need(x, "x")
         B, S, Hd = x.shape
         D = wq.shape[0] // nh
@@ -1400,19 +1349,12 @@ class _QKVRopeAttentionFn(torch.autograd.Function):
         _rope_launch(qk, qk, cos, sin, False)
         scale = 1.0 / math.sqrt(D)
         # O^T for the out-projection's wgrad (TT form), written by the attention epilogue for free
-        o_t = None
-        if os.getenv("PICO_XT_WGRAD", "1") != "0":
-            o_t = _pair_xt(out_hint, nh * D, B * S, x)
-            if o_t is None:
-                o_t = torch.empty((nh * D, B * S), dtype=x.dtype, device=x.device)
+        o_t = WO.xt_sink(out_hint, nh * D, B * S, x)
         o, lse = attention_block_fwd(q, k, v, scale, causal, o_t=o_t, rope_q=(cos, sin) if fuse_q else None)
-        ctx.save_for_backward(_wgrad_input(x2, N, x), W, qkv, o, lse, cos, sin)
+        ctx.save_for_backward(WO.saved_input(x2, N, x), W, qkv, o, lse, cos, sin)
         ctx.params = (wq, wk, wv)
         ctx.meta = (B, S, Hd, nh, nkv, D, causal, scale)
-        out = o.view(B, S, nh * D)
-        if o_t is not None:
-            out._pico_t = o_t
-        return out
+        return WO.attach_t(o.view(B, S, nh * D), o_t)
 
     @staticmethod
     def backward(ctx, do):
@@ -1421,9 +1363,8 @@ class _QKVRopeAttentionFn(torch.autograd.Function):
         N = W.shape[0]
         heads = qkv.view(B, S, N // D, D)
         q, k, v = heads[:, :, :nh], heads[:, :, nh:nh + nkv], heads[:, :, nh + nkv:]
-        from . import wgrad_pair as WP
-        # the q|k|v dy pair buffer when the forward paired this micro-batch's x^T (wgrad_pair)
-        dqkv = WP.dy_out_if_paired(ctx.params[0], x2, N, Hd, B * S, qkv.dtype, qkv.device)
+        # the q|k|v dy group slot when the forward put this micro-batch's x^T into its slot
+        dqkv = WO.dy_sink_of_input(ctx.params[0], x2, N, Hd, B * S, qkv)
         if dqkv is None:
             dqkv = torch.empty_like(qkv)
         dheads = dqkv.view(B, S, N // D, D)

@@ -19,6 +19,7 @@ import torch.distributed as dist
 
 from .. import ops
 from .. import process_group_manager as pgm
+from .. import wgrad_operands
 from .tp_communications import all_reduce_
 
 
@@ -193,7 +194,7 @@ class _VocabParallelLMHeadCEFn(torch.autograd.Function):
         lse, loss_rows = _kernel_stats(logits, t, rank * vl, world * vl, ignore_index, group, world)
         stats = ops.ce_count(t, ignore_index)  # [n_valid, 1 / n_valid]
         ops.ce_vp_grad(logits, t, lse, stats[1:], rank * vl, world * vl, ignore_index, out=logits)
-        ctx.save_for_backward(logits, ops._wgrad_input(x2, vl, x), w)
+        ctx.save_for_backward(logits, wgrad_operands.saved_input(x2, vl, x), w)
         ctx.group, ctx.world, ctx.xshape = group, world, x.shape
         return ops.ce_mean(loss_rows, stats, x.dtype)
 
