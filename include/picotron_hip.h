@@ -47,6 +47,8 @@
  *                                 the nn.Linear wgrad / dgrad GEMMs (ref picotron/model.py nn.Linear)
  *   pico_kv_append, pico_attn_decode
  *                             <- no reference call: KV-cache generation (picotron_amd/generate.py)
+ *   pico_sample               <- no reference call: the fused next-token sampler of generation (temperature,
+ *                                 top-k, top-p, counter-based draw; all per-step state on the device)
  *
  * Conventions: all pointers are device pointers allocated by the caller (kernels never
  * allocate); bf16 tensors are passed as raw 16-bit storage; `stream` is a hipStream_t
@@ -483,6 +485,31 @@ int pico_attn_decode(const void* q, const int64_t* q_strides, const void* k_cach
                      const void* v_cache, const int64_t* v_strides, const int32_t* seqlens, void* o, float* lse,
                      void* workspace, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t s_max,
                      int64_t head_dim, float softmax_scale, int64_t split_keys, void* stream);
+
+/* ---- Generation: fused device sampler (no reference call: the reference has no sampling path) ----
+ * pico_sample: one launch per decode step, one workgroup per row of logits [rows, vocab] (dtype PICO_SAMPLE_F32 or
+ *   PICO_SAMPLE_BF16, row r at logits + r * row_stride elements, unit last stride, 1 <= vocab <= 2^20, no
+ *   alignment beyond the element's). All per-step state is on the DEVICE, so a captured launch replays with the
+ *   same arguments:
+ *   params: 8 words {f32 temperature, f32 top_p (<= 0 or >= 1: off), i32 top_k (<= 0 or >= vocab: off), i32 eos
+ *     (< 0: none), i32 pad, u32 seed low word, u32 seed high word, 0}, read at run time;
+ *   draws int32 [rows]: row r reads its draw counter n = draws[r] and stores n + 1;
+ *   done uint8 [rows] (may be NULL), tokens int64 [rows], out int64 [rows, out_cols] with row stride out_stride (may
+ *     be NULL), kept int32 [rows] (may be NULL): the size of the set the token was drawn from.
+ *   Per row, in fp32 (NaN counts as -inf, +inf as FLT_MAX): temperature <= 0 takes the maximum's lowest index (kept
+ *   1). Otherwise masses exp((x - max x) / temperature); top-k keeps {x >= the k-th largest value} (ties kept);
+ *   top-p then keeps {x >= t} within it for the largest t whose mass reaches top_p times the top-k set's mass (ties
+ *   kept); the token is the first kept index in vocabulary order whose inclusive cumulative mass exceeds u times
+ *   the kept mass, u = ((w[1] << 32) | w[0]) / 2^64 with w = Philox4x32-10(counter {r, n, 0, 0}, key {seed low,
+ *   seed high}). A row with no finite logit gives token 0, kept 0. done[r] set: token = pad, kept 0. Then tokens[r]
+ *   = token, out[r, n] = token if 0 <= n < out_cols, done[r] |= (token == eos) if eos >= 0, draws[r] = n + 1.
+ *   Thresholds and the draw are integer arithmetic on fixed-point masses round(w 2^40): the same inputs give the
+ *   same token on every run, whatever the other rows hold. rows == 0 is a no-op. Timed under PICO_K_CE_FWD. */
+#define PICO_SAMPLE_F32 0
+#define PICO_SAMPLE_BF16 1
+int pico_sample(const void* logits, int dtype, int64_t row_stride, int64_t rows, int64_t vocab, const void* params,
+                int32_t* draws, uint8_t* done, int64_t* tokens, int64_t* out, int64_t out_stride, int64_t out_cols,
+                int32_t* kept, void* stream);
 
 #ifdef __cplusplus
 }

@@ -128,6 +128,8 @@ _SIGNATURES = {
     "pico_attn_decode": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
                                         ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
                                         c_i64, ctypes.c_float, c_i64, c_vp]),
+    "pico_sample": (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                   c_vp, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

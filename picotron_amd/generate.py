@@ -13,10 +13,16 @@ rounding points), which is the reference the tests compare the kernels with. A H
 error: there is no eager path on the device.
 
 A decode step performs no host synchronisation: positions and lengths live on the device, shapes are fixed.
+
+`sample_tokens` is the fused sampler (`pico_sample`: temperature, top-k, top-p, a Philox draw, the EOS / pad rule
+and the output column in one launch, every per-step value in a `SamplerState` on the device); with it a whole
+iteration, decode step and sampler, is captured once as a HIP graph and replayed per token (`generate(graph=True)`).
 """
 import math
 import os
+import struct
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -251,6 +257,7 @@ class KVCache:
         self.lens = torch.zeros(batch, dtype=torch.int32, device=device)
         self.batch, self.max_len = batch, max_len
         self._plan, self._plan_model = None, None  # prefill's per-layer table (_layer_plan)
+        self._graph, self.graph_captures = None, 0  # generate(graph=True)'s captured iteration (_DecodeGraph)
 
     def reset(self):
         self.lens.zero_()
@@ -391,14 +398,212 @@ def sample_next(logits, temperature=0.0, top_k=None, generator=None):
     return torch.multinomial(torch.softmax(x, dim=-1), 1, generator=generator).squeeze(-1)
 
 
-@torch.no_grad()
-def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0, top_k=None, eos_token_id=None,
-             pad_token_id=0, generator=None, return_logits=False, cache=None):
-    """Sample max_new_tokens tokens per row after the (right-padded) prompts: int64 [B, max_new_tokens], and with
-    return_logits the fp32 [B, max_new_tokens, V] each token was drawn from. One prefill, then max_new_tokens - 1
-    decode steps. A row that has emitted eos_token_id yields pad_token_id from then on (masked on the device; no
-    early exit, no per-step synchronisation). cache: a KVCache to reuse (reset here), else one of exactly the
-    needed length is allocated."""
+# --------------------------------------------------------------------------------------------
+# Fused device sampler
+# --------------------------------------------------------------------------------------------
+_KEEP = object()
+_F32_MAX = float(np.finfo(np.float32).max)
+_PARAMS = struct.Struct("<ffiiiIII")  # csrc/sample.hip SampleParams
+
+
+class SamplerState:
+    """What pico_sample reads and writes on the device, so that a captured launch replays with the same arguments:
+    .params (8 words: temperature, top_p, top_k, eos, pad, seed low / high), .draws int32 [batch] (draws made per
+    row: the Philox counter and the column of .out), .done uint8 [batch] (row has emitted EOS), .tokens int64 [batch]
+    (the last step's tokens), .kept int32 [batch] (size of the set the last token was drawn from) and optionally
+    .out int64 [batch, cols] (unit last stride), of which step n writes column n.
+
+    set() rewrites .params in place (a copy_ into the same tensor: a captured graph sees the new settings);
+    reset() zeroes .draws and .done. seed=None takes torch.initial_seed()."""
+
+    def __init__(self, batch, device, temperature=0.0, top_k=None, top_p=None, eos_token_id=None, pad_token_id=0,
+                 seed=None, out=None):
+        if batch <= 0:
+            raise ValueError("SamplerState: batch must be positive")
+        self.params = torch.zeros(8, dtype=torch.int32, device=device)
+        device = self.params.device  # with its index
+        self.batch, self.device = int(batch), device
+        if out is not None and (out.dim() != 2 or out.shape[0] != batch or out.dtype != torch.int64
+                                or out.device != device or (out.shape[1] > 1 and out.stride(1) != 1)):
+            raise ValueError("SamplerState: out must be int64 [batch, cols] on the device with unit last stride")
+        self.out = out
+        self.draws = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.done = torch.zeros(batch, dtype=torch.uint8, device=device)
+        self.tokens = torch.zeros(batch, dtype=torch.int64, device=device)
+        self.kept = torch.zeros(batch, dtype=torch.int32, device=device)
+        self._host = dict(temperature=0.0, top_k=None, top_p=None, eos_token_id=None, pad_token_id=0, seed=None)
+        self.set(temperature=temperature, top_k=top_k, top_p=top_p, eos_token_id=eos_token_id,
+                 pad_token_id=pad_token_id, seed=seed)
+
+    def set(self, temperature=_KEEP, top_k=_KEEP, top_p=_KEEP, eos_token_id=_KEEP, pad_token_id=_KEEP, seed=_KEEP):
+        h = dict(self._host)
+        for k, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("eos_token_id", eos_token_id),
+                     ("pad_token_id", pad_token_id), ("seed", seed)):
+            if v is not _KEEP:
+                h[k] = v
+        if h["seed"] is None:
+            h["seed"] = torch.initial_seed()
+        if not h["temperature"] >= 0:
+            raise ValueError("SamplerState: temperature must be >= 0")
+        if h["top_k"] is not None and h["top_k"] < 1:
+            raise ValueError("SamplerState: top_k must be >= 1")
+        if h["top_p"] is not None and not 0 < h["top_p"] <= 1:
+            raise ValueError("SamplerState: top_p must lie in (0, 1]")
+        if h["eos_token_id"] is not None and h["eos_token_id"] < 0:
+            raise ValueError("SamplerState: eos_token_id must be >= 0")
+        seed = int(h["seed"]) & 0xFFFFFFFFFFFFFFFF
+        words = _PARAMS.pack(float(h["temperature"]), 0.0 if h["top_p"] is None else float(h["top_p"]),
+                             0 if h["top_k"] is None else min(int(h["top_k"]), 2 ** 31 - 1),
+                             -1 if h["eos_token_id"] is None else int(h["eos_token_id"]), int(h["pad_token_id"]),
+                             seed & 0xFFFFFFFF, seed >> 32, 0)
+        self.params.copy_(torch.frombuffer(bytearray(words), dtype=torch.int32))
+        self._host = h
+        return self
+
+    def reset(self):
+        self.draws.zero_()
+        self.done.zero_()
+        return self
+
+
+def _philox4x32_10(c0, c1, k0, k1):
+    """Philox4x32-10 on uint64 numpy arrays holding 32-bit words, counter (c0, c1, 0, 0), key (k0, k1): the four output
+    words (csrc/optim_common.h philox4x32_10)."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c0, c1 = c0.astype(np.uint64) & m32, c1.astype(np.uint64) & m32
+    c2, c3 = np.zeros_like(c0), np.zeros_like(c0)
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        a, b = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        n0, n2 = (b >> np.uint64(32)) ^ c1 ^ k0, (a >> np.uint64(32)) ^ c3 ^ k1
+        c1, c3, c0, c2 = b & m32, a & m32, n0, n2
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0, c1, c2, c3
+
+
+def _sample_reference(logits, state):
+    """pico_sample's contract in plain torch, on CPU tensors: fp64 masses (the kernel: fp32 exp, fixed-point sums),
+    the same Philox draw, the same state updates."""
+    B, V = logits.shape
+    temperature, top_p, top_k, eos, pad, seed_lo, seed_hi, _ = _PARAMS.unpack(state.params.numpy().tobytes())
+    x = logits.to(torch.float64)
+    x = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x).clamp(max=_F32_MAX)
+    xmax = x.max(dim=-1, keepdim=True).values
+    live = (xmax > float("-inf")).squeeze(-1)
+    index = torch.arange(V)
+    first_max = torch.where(x == xmax, index, V).min(dim=-1).values
+    if not temperature > 0:
+        tok, kept = first_max, torch.ones(B, dtype=torch.int64)
+    else:
+        w = torch.exp((x - torch.where(live[:, None], xmax, torch.zeros_like(xmax))) / temperature)
+        keep = torch.ones(B, V, dtype=torch.bool)
+        if 0 < top_k < V:
+            keep &= x >= torch.topk(x, top_k, dim=-1).values[:, -1:]
+        if 0 < top_p < 1:
+            wk = w * keep
+            xs, order = torch.sort(torch.where(keep, x, torch.full_like(x, float("-inf"))), dim=-1, descending=True,
+                                   stable=True)
+            csum = wk.gather(-1, order).cumsum(-1)
+            target = np.float64(np.float32(top_p)).item() * wk.sum(-1, keepdim=True)
+            # the first sorted position whose cumulative mass reaches the target carries the threshold value: a tie
+            # group's full mass sits at its last position, so no larger value reaches the target
+            j = (csum >= target).to(torch.int8).argmax(dim=-1, keepdim=True)
+            keep &= x >= xs.gather(-1, j)
+        rows = np.arange(B, dtype=np.uint64)
+        w0, w1, _, _ = _philox4x32_10(rows, state.draws.numpy().astype(np.int64).astype(np.uint64), seed_lo, seed_hi)
+        r = [(int(hi) << 32) | int(lo) for lo, hi in zip(w0, w1)]
+        u = torch.tensor([ri / 2.0 ** 64 for ri in r], dtype=torch.float64)
+        cum = (w * keep).cumsum(-1)
+        last = torch.where(keep & (w > 0), index, -1).max(dim=-1).values.clamp(min=0)
+        tok = torch.minimum(torch.searchsorted(cum, (u * cum[:, -1])[:, None], right=True).squeeze(-1), last)
+        kept = keep.sum(-1)
+    tok = torch.where(live, tok, torch.zeros_like(tok))
+    kept = torch.where(live, kept, torch.zeros_like(kept))
+    was_done = state.done != 0
+    tok = torch.where(was_done, torch.full_like(tok, pad), tok)
+    kept = torch.where(was_done, torch.zeros_like(kept), kept)
+    state.tokens.copy_(tok)
+    state.kept.copy_(kept.to(torch.int32))
+    if state.out is not None:
+        for b in range(B):
+            n = int(state.draws[b])
+            if 0 <= n < state.out.shape[1]:
+                state.out[b, n] = tok[b]
+    if eos >= 0:
+        state.done |= (tok == eos).to(torch.uint8)
+    state.draws += 1
+
+
+def sample_tokens(logits, state, *, return_kept=False):
+    """Next tokens int64 [B] from logits [B, V] (fp32 or bf16, unit last stride, any row stride) under the settings
+    of `state` (SamplerState): temperature, then top-k, then top-p (HF's warper order, ties at either threshold
+    kept), then a Philox draw with counter (row, state.draws[row]); argmax (lowest index on ties) at temperature 0.
+    NaN counts as -inf, +inf as the largest finite fp32; a row with no finite logit yields token 0 (kept 0). A row
+    whose state.done is set yields the pad token; a drawn EOS sets it. Step n writes column n of state.out.
+
+    One pico_sample launch for HIP tensors, no host synchronisation; for CPU tensors the plain-torch restatement.
+    Returns state.tokens (and state.kept with return_kept): the state's own buffers, overwritten by the next call."""
+    if not isinstance(state, SamplerState):
+        raise TypeError("sample_tokens: state must be a SamplerState")
+    if logits.dim() != 2 or logits.shape[0] != state.batch or logits.shape[1] < 1:
+        raise ValueError(f"sample_tokens: logits must be [batch = {state.batch}, vocab]")
+    if logits.device != state.device:
+        raise ValueError(f"sample_tokens: logits on {logits.device}, the state on {state.device}")
+    B, V = logits.shape
+    if V > 1 and logits.stride(1) != 1:
+        raise ValueError("sample_tokens: logits rows must be unit-stride")
+    if logits.device.type == "cpu":
+        if not logits.dtype.is_floating_point:
+            raise TypeError("sample_tokens: logits must be floating point")
+        _sample_reference(logits, state)
+    else:
+        if logits.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"sample_tokens: {logits.dtype} logits on {logits.device}: the kernel takes fp32 or bf16 "
+                            "(there is no eager path on the device)")
+        out = state.out
+        _lib.check(_lib.load().pico_sample(
+            _lib.ptr(logits), 0 if logits.dtype == torch.float32 else 1, logits.stride(0), B, V,
+            _lib.ptr(state.params), _lib.ptr(state.draws), _lib.ptr(state.done), _lib.ptr(state.tokens),
+            _lib.ptr(out), out.stride(0) if out is not None else 0, out.shape[1] if out is not None else 0,
+            _lib.ptr(state.kept), _lib.stream_of(logits)), "pico_sample")
+    return (state.tokens, state.kept) if return_kept else state.tokens
+
+
+class _DecodeGraph:
+    """One captured decode iteration: decode_step(model, state.tokens, cache) then sample_tokens, on the state's
+    static buffers. key: the batch and the data pointers the graph has baked in. It holds what those pointers point
+    into and no one else keeps alive: the sampler state, the static logits, and the decode attention workspace that
+    was current at capture (_WORKSPACES replaces its entry when a larger one is needed; the graph keeps its own)."""
+
+    def __init__(self, key, model, graph, state, logits, workspace):
+        self.key, self.model, self.graph, self.state, self.logits = key, model, graph, state, logits
+        self.workspace = workspace
+
+    def fits(self, model, key):
+        return self.model is model and self.key == key + (self.workspace.data_ptr(),)
+
+
+def _graph_key(model, cache):
+    ptrs = [cache.lens.data_ptr(), model.embedding.weight.data_ptr(), model.final_norm.weight.data_ptr(),
+            model.final_proj.weight.data_ptr()]
+    for entry in cache._plan:
+        ptrs.extend(t.data_ptr() for t in entry if isinstance(t, torch.Tensor))
+    return (cache.batch, tuple(ptrs))
+
+
+def _capture_stream(device):
+    """The stream torch.cuda.graph captures on by default, created here if no capture has run yet: the warm-up
+    iteration runs on it, so that decode_step's workspace (keyed by stream) and the GEMM library's exist before the
+    capture and are the ones the graph bakes in."""
+    if torch.cuda.graph.default_capture_stream is None:
+        with torch.cuda.device(device):
+            torch.cuda.graph.default_capture_stream = torch.cuda.Stream()
+    return torch.cuda.graph.default_capture_stream
+
+
+def _generate_cache(model, input_ids, max_new_tokens, cache):
+    """generate()'s checks of its arguments, and the cache it runs on: the caller's, reset, or a new one of exactly
+    the needed length."""
     _check_model(model)
     if input_ids.dim() != 2:
         raise ValueError("generate: input_ids must be [batch, tokens]")
@@ -410,13 +615,97 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
         if need > model.max_position_embeddings:
             raise ValueError(f"generate: prompt {T} + {max_new_tokens} new tokens exceed the model's "
                              f"max_position_embeddings {model.max_position_embeddings}")
-        cache = KVCache(model, B, need, device=input_ids.device)
-    else:
-        _check_cache(model, cache, B)
-        if need > cache.max_len:
-            raise ValueError(f"generate: prompt {T} + {max_new_tokens} new tokens exceed the cache's max_len "
-                             f"{cache.max_len}")
-        cache.reset()
+        return KVCache(model, B, need, device=input_ids.device)
+    _check_cache(model, cache, B)
+    if need > cache.max_len:
+        raise ValueError(f"generate: prompt {T} + {max_new_tokens} new tokens exceed the cache's max_len "
+                         f"{cache.max_len}")
+    cache.reset()
+    return cache
+
+
+def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p, eos_token_id,
+                    pad_token_id, seed, return_logits, cache, graph):
+    cache = _generate_cache(model, input_ids, max_new_tokens, cache)
+    B, N = input_ids.shape[0], max_new_tokens
+    dev = input_ids.device
+    settings = dict(temperature=temperature, top_k=top_k, top_p=top_p, eos_token_id=eos_token_id,
+                    pad_token_id=pad_token_id, seed=seed)
+    keep = torch.empty((B, N, model.vocab_size), dtype=torch.float32, device=dev) if return_logits else None
+    logits = prefill(model, input_ids, cache, prompt_lens)
+    if keep is not None:
+        keep[:, 0] = logits
+    if not graph:
+        state = SamplerState(B, dev, out=torch.empty((B, N), dtype=torch.int64, device=dev), **settings)
+        sample_tokens(logits, state)
+        for step in range(1, N):
+            logits = decode_step(model, state.tokens, cache)
+            if keep is not None:
+                keep[:, step] = logits
+            sample_tokens(logits, state)
+        return (state.out, keep) if return_logits else state.out
+
+    from .train import _capturing
+    key = _graph_key(model, cache)
+    held = cache._graph if cache._graph is not None and cache._graph.fits(model, key) else None
+    if held is not None:
+        state = held.state.set(**settings).reset()
+    else:  # the graph writes column n of a static out as wide as the cache: any later call's tokens fit
+        state = SamplerState(B, dev, out=torch.empty((B, cache.max_len), dtype=torch.int64, device=dev), **settings)
+    sample_tokens(logits, state)
+    first = 1
+    if held is None and N > 1:
+        # one eager iteration on the capture stream (it is generated token 1), then the capture of the same two calls
+        cache._graph = None
+        side = _capture_stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            logits = decode_step(model, state.tokens, cache)
+            sample_tokens(logits, state)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        if keep is not None:
+            keep[:, 1] = logits
+            logits.record_stream(torch.cuda.current_stream(dev))  # allocated on `side`, read here
+        g = torch.cuda.CUDAGraph()
+        with _capturing(g):
+            static_logits = decode_step(model, state.tokens, cache)
+            sample_tokens(static_logits, state)
+        # the workspace the two passes above used on this stream (decode attention's partials): the graph points
+        # into it, so the graph holds it; a later, larger request replaces the dict's entry, not this tensor
+        workspace = _WORKSPACES[(static_logits.device, side.cuda_stream)]
+        held = cache._graph = _DecodeGraph(key + (workspace.data_ptr(),), model, g, state, static_logits, workspace)
+        cache.graph_captures += 1
+        first = 2
+    for step in range(first, N):
+        held.graph.replay()
+        if keep is not None:
+            keep[:, step] = held.logits
+    out = state.out[:, :N].clone()
+    return (out, keep) if return_logits else out
+
+
+@torch.no_grad()
+def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0, top_k=None, eos_token_id=None,
+             pad_token_id=0, generator=None, return_logits=False, cache=None, top_p=None, seed=None, graph=False):
+    """Sample max_new_tokens tokens per row after the (right-padded) prompts: int64 [B, max_new_tokens], and with
+    return_logits the fp32 [B, max_new_tokens, V] each token was drawn from. One prefill, then max_new_tokens - 1
+    decode steps. A row that has emitted eos_token_id yields pad_token_id from then on (masked on the device; no
+    early exit, no per-step synchronisation). cache: a KVCache to reuse (reset here), else one of exactly the
+    needed length is allocated.
+
+    top_p, seed or graph=True select the fused device sampler (sample_tokens: one launch per token, temperature /
+    top_k / top_p in HF's order, Philox draws keyed by `seed`, default torch.initial_seed(); the tokens are a pure
+    function of the logits and the seed). graph=True also captures one decode iteration (decode_step + the sampler)
+    as a HIP graph and replays it per token; the graph lives on `cache` and is reused by later calls with the same
+    model and batch, whatever their settings. generator= belongs to the default path only."""
+    if top_p is not None or seed is not None or graph:
+        if generator is not None:
+            raise ValueError("generate: generator= cannot be combined with top_p / seed / graph (the fused sampler "
+                             "draws from its seed)")
+        return _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p,
+                               eos_token_id, pad_token_id, seed, return_logits, cache, graph)
+    cache = _generate_cache(model, input_ids, max_new_tokens, cache)
+    B = input_ids.shape[0]
     dev = input_ids.device
     out = torch.empty((B, max_new_tokens), dtype=torch.int64, device=dev)
     keep = torch.empty((B, max_new_tokens, model.vocab_size), dtype=torch.float32, device=dev) if return_logits \
