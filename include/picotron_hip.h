@@ -49,6 +49,8 @@
  *                             <- no reference call: KV-cache generation (picotron_amd/generate.py)
  *   pico_sample               <- no reference call: the fused next-token sampler of generation (temperature,
  *                                 top-k, top-p, counter-based draw; all per-step state on the device)
+ *   pico_decode_linear        <- no reference call: a decode step's nn.Linear at 1..16 rows, with the RMSNorm before
+ *                                 it and the SwiGLU after it in the same launch
  *
  * Conventions: all pointers are device pointers allocated by the caller (kernels never
  * allocate); bf16 tensors are passed as raw 16-bit storage; `stream` is a hipStream_t
@@ -95,7 +97,8 @@ enum {
   PICO_K_ATTN_BWD_Q = 23,  /* split backward: dQ query-major kernel (+ delta, LSE*log2e) */
   PICO_K_GRAD_SQNORM = 24, /* global gradient norm: the per-chunk sum-of-squares kernel */
   PICO_K_GRAD_SCALE = 25,  /* standalone gradient clip (pico_adamw_bf16_clip is timed under PICO_K_ADAMW) */
-  PICO_K_COUNT = 26
+  PICO_K_DECODE_LINEAR = 26, /* pico_decode_linear: the stream and, under a K split, its finishing launch */
+  PICO_K_COUNT = 27
 };
 
 int pico_abi_version(void);
@@ -510,6 +513,51 @@ int pico_attn_decode(const void* q, const int64_t* q_strides, const void* k_cach
 int pico_sample(const void* logits, int dtype, int64_t row_stride, int64_t rows, int64_t vocab, const void* params,
                 int32_t* draws, uint8_t* done, int64_t* tokens, int64_t* out, int64_t out_stride, int64_t out_cols,
                 int32_t* kept, void* stream);
+
+/* ---- Generation: skinny weight-streaming linear (no reference call: a decode step's projections at 1..16 rows) ----
+ * pico_decode_linear: y[m, n] = epilogue(prologue(x)[m, k] . weight[n, k]^T), 1 <= m <= 16 (m == 0 is a no-op), fp32
+ *   accumulation on the matrix pipe, every element of weight read once.
+ *   x [m, k] bf16, row stride ldx; weight [n, k] bf16, row stride ldw (nn.Linear.weight, or stacked weights); k a
+ *   multiple of 32, n a multiple of 8 (SWIGLU: of 16), every stride a multiple of 8 elements, every pointer 16-byte
+ *   aligned; a violation returns PICO_EINVAL with a message.
+ *   Prologue (norm_weight != NULL, [k] bf16): xe = bf16(x + residual) (residual [m, k] bf16 with row stride ldr, or
+ *   NULL: xe = x), rstd = rsqrt(mean(xe^2) + eps) in fp32, h = bf16(xe rstd norm_weight) takes the place of x:
+ *   pico_rmsnorm_fwd's arithmetic and rounding points. residual_out ([m, k] bf16, row stride ldro, or NULL) receives
+ *   xe from one workgroup; it must not overlap x or residual (other workgroups are still reading them: refused).
+ *   residual / residual_out without norm_weight are refused.
+ *   Epilogue: PICO_DL_BF16 y = bf16(acc), y [m, n] bf16; PICO_DL_F32 y = float(bf16(acc)), y [m, n] fp32 (the LM
+ *   head followed by .float()); PICO_DL_SWIGLU weight is the stacked gate|up matrix [2 i, k] and y [m, i] bf16 =
+ *   bf16(silu(g) u) on g = bf16(acc_gate), u = bf16(acc_up): the GEMM output's rounding, then pico_swiglu_fwd's
+ *   arithmetic. ldy is y's row stride in its own elements.
+ *   A workgroup owns 32 rows of weight (SWIGLU: 16 + 16) over a slice of k; its four waves share the slice and are
+ *   added in wave order. split_k > 1 cuts k into that many slices across workgroups (evened out to multiples of 32;
+ *   a slice may hold at most 2048 columns: a smaller split is refused), each writing an fp32 partial [m, n] to the
+ *   workspace; a finishing launch adds them in slice order. split_k <= 0 selects pico_decode_linear_split_k (a host
+ *   rule on n, k, the epilogue and the CU count; m does not enter). No atomics, no inter-workgroup waiting: the
+ *   same inputs and split_k give the same bits, and a row's result depends neither on the other rows nor on m.
+ *   workspace: pico_decode_linear_workspace_bytes for the same shape (0 when there is one slice: workspace may be
+ *   NULL; -1 for bad arguments). Timed under PICO_K_DECODE_LINEAR. */
+#define PICO_DL_BF16 0
+#define PICO_DL_F32 1
+#define PICO_DL_SWIGLU 2
+typedef struct pico_decode_linear_args {
+  const void* x;
+  const void* weight;
+  void* y;
+  const void* norm_weight;
+  const void* residual;
+  void* residual_out;
+  void* workspace;
+  int64_t ldx, ldw, ldy, ldr, ldro;
+  int64_t m, n, k;
+  int64_t split_k;
+  float eps;
+  int epilogue;
+} pico_decode_linear_args;
+int64_t pico_decode_linear_args_size(void);
+int64_t pico_decode_linear_split_k(int64_t n, int64_t k, int epilogue);
+int64_t pico_decode_linear_workspace_bytes(int64_t m, int64_t n, int64_t k, int epilogue, int64_t split_k);
+int pico_decode_linear(const pico_decode_linear_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@ K_ATTN_BWD, K_ATTN_BWD_DQ, K_GRAD_ACCUM, K_CAST, K_SCALE, K_ATTN_MERGE = 9, 10, 
 K_EMBEDDING_BWD, K_CE_FWD, K_CE_BWD, K_TRANSPOSE, K_ATTN_BWD_DKV, K_SORT_IDS, K_ADAMW = 15, 16, 17, 18, 19, 20, 21
 K_ATTN_BWD_KV, K_ATTN_BWD_Q = 22, 23
 K_GRAD_SQNORM, K_GRAD_SCALE = 24, 25
+K_DECODE_LINEAR = 26
 KERNEL_NAMES = {
     K_RMSNORM_FWD: "rmsnorm_fwd", K_RMSNORM_BWD: "rmsnorm_bwd", K_RMSNORM_DW: "rmsnorm_dw", K_ROPE: "rope",
     K_SWIGLU_FWD: "swiglu_fwd", K_SWIGLU_BWD: "swiglu_bwd", K_ATTN_FWD: "attn_fwd",
@@ -27,7 +28,7 @@ KERNEL_NAMES = {
     K_EMBEDDING_BWD: "embedding_bwd", K_CE_FWD: "cross_entropy_fwd", K_CE_BWD: "cross_entropy_bwd",
     K_TRANSPOSE: "transpose_bf16", K_ATTN_BWD_DKV: "attn_bwd_dkv", K_SORT_IDS: "sort_ids", K_ADAMW: "adamw",
     K_ATTN_BWD_KV: "attn_bwd_kv", K_ATTN_BWD_Q: "attn_bwd_q",
-    K_GRAD_SQNORM: "grad_sqnorm", K_GRAD_SCALE: "grad_scale",
+    K_GRAD_SQNORM: "grad_sqnorm", K_GRAD_SCALE: "grad_scale", K_DECODE_LINEAR: "decode_linear",
 }
 
 # kernel-selection knobs (pico_select; PICO_SEL_* in include/picotron_hip.h)
@@ -53,6 +54,20 @@ class AttnArgs(ctypes.Structure):
         ("do_strides", c_i64 * 3), ("dq_strides", c_i64 * 3), ("dk_strides", c_i64 * 3), ("dv_strides", c_i64 * 3),
         ("softmax_scale", ctypes.c_float), ("causal", ctypes.c_int), ("flags", ctypes.c_int),
         ("rope_cos", c_vp), ("rope_sin", c_vp), ("rope_stride", c_i64), ("o_t", c_vp), ("o_t_ld", c_i64),
+    ]
+
+
+DL_BF16, DL_F32, DL_SWIGLU = 0, 1, 2  # pico_decode_linear epilogues (PICO_DL_*)
+
+
+class DecodeLinearArgs(ctypes.Structure):
+    """Mirror of `pico_decode_linear_args`."""
+    _fields_ = [
+        ("x", c_vp), ("weight", c_vp), ("y", c_vp), ("norm_weight", c_vp), ("residual", c_vp),
+        ("residual_out", c_vp), ("workspace", c_vp),
+        ("ldx", c_i64), ("ldw", c_i64), ("ldy", c_i64), ("ldr", c_i64), ("ldro", c_i64),
+        ("m", c_i64), ("n", c_i64), ("k", c_i64), ("split_k", c_i64),
+        ("eps", ctypes.c_float), ("epilogue", ctypes.c_int),
     ]
 
 
@@ -130,6 +145,10 @@ _SIGNATURES = {
                                         c_i64, ctypes.c_float, c_i64, c_vp]),
     "pico_sample": (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                    c_vp, c_vp]),
+    "pico_decode_linear_args_size": (c_i64, []),
+    "pico_decode_linear_split_k": (c_i64, [c_i64, c_i64, ctypes.c_int]),
+    "pico_decode_linear_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, ctypes.c_int, c_i64]),
+    "pico_decode_linear": (ctypes.c_int, [ctypes.POINTER(DecodeLinearArgs), c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

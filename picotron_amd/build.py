@@ -35,6 +35,11 @@ FILE_FLAGS = {
     **{f: SPLIT_BWD_FLAGS for f in SPLIT_BWD_SOURCES},
     "attn_fwd.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
     "attn_fwdp.hip": ["-fno-slp-vectorize", "-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form"],
+    # no packed fp32 VALU beside the MFMAs, as for the attention kernels above: without the flag the SLP vectoriser
+    # packs the norm prologue and the epilogues into 153 v_pk_{mul,add,fma}_f32 (with it: none; same registers, no
+    # scratch either way). -fno-slp-vectorize would do as well for today's code; the target feature also covers what
+    # later passes may form. Not measured apart for this kernel.
+    "decode_linear.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

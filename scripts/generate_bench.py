@@ -8,7 +8,8 @@ device; reads nothing outside the repository.
            rounds, medians reported; the time of the kernel alone from the library's per-launch events.
   e2e      SmolLM-1.7B geometry, --layers layers (15), B in {1, 8}, 128-token prompt, 128 new tokens: ms per
            generated token of generate() on its default path (the loop as it was before the fused sampler), of the
-           fused sampler run eagerly, and of graph=True (captured before the clock starts), greedy and with
+           fused sampler run eagerly, of graph=True and of graph=True with skinny_linear=True (the projections on
+           pico_decode_linear; both captured before the clock starts, each on its own cache), greedy and with
            T 0.8 / top-k 50 / top-p 0.9; host clock around the whole call ending in a synchronise, alternated for
            --rounds rounds, medians. The decode step over the weight-streaming floor as scripts/decode_bench.py
            defines it (prefill taken from the same rounds).
@@ -134,11 +135,13 @@ def e2e(args):
     for B in (1, 8):
         prompt = torch.randint(0, cfg.vocab_size, (B, P), generator=torch.Generator().manual_seed(B)).to(dev)
         cache = G.KVCache(model, B, P + N)
+        skinny_cache = G.KVCache(model, B, P + N)  # a cache holds one captured graph: the skinny route keeps its own
         out = {}
 
         def run(name, **kw):
             def fn():
-                out[name] = G.generate(model, prompt, N, cache=cache, **kw)
+                out[name] = G.generate(model, prompt, N, cache=skinny_cache if kw.get("skinny_linear") else cache,
+                                       **kw)
             return fn
 
         def prefill_only():
@@ -148,10 +151,12 @@ def e2e(args):
         forms = {"default_greedy": run("default_greedy"),
                  "fused_eager_greedy": run("fused_eager_greedy", seed=1),
                  "graph_greedy": run("graph_greedy", graph=True),
+                 "skinny_graph_greedy": run("skinny_graph_greedy", graph=True, skinny_linear=True),
                  "default_top_k": run("default_top_k", temperature=0.8, top_k=50,
                                       generator=torch.Generator(dev).manual_seed(1)),
                  "fused_eager_sampled": run("fused_eager_sampled", **sampled),
                  "graph_sampled": run("graph_sampled", graph=True, **sampled),
+                 "skinny_graph_sampled": run("skinny_graph_sampled", graph=True, skinny_linear=True, **sampled),
                  "prefill": prefill_only}
         for name, fn in forms.items():  # one warm pass: code objects, GEMM algorithms, the capture
             _clock_ms(fn)
@@ -170,6 +175,12 @@ def e2e(args):
             rec[name + "_ms_rounds"] = [round(x, 1) for x in ms[name]]
             rec[name + "_ms_per_token"] = round(med[name] / N, 3)
             rec[name + "_step_over_floor"] = round((med[name] - med["prefill"]) / (N - 1) / floor_ms, 2)
+        for kind in ("greedy", "sampled"):  # the skinny route against the replayed default route, with the spread
+            a, b = ms["skinny_graph_" + kind], ms["graph_" + kind]
+            rec[f"skinny_over_graph_{kind}"] = round(med["skinny_graph_" + kind] / med["graph_" + kind], 3)
+            rec[f"skinny_vs_graph_{kind}_spread_ms"] = round(max(max(a) - min(a), max(b) - min(b)), 1)
+        rec["skinny_greedy_tokens_equal_fraction_vs_graph"] = round(
+            float((out["skinny_graph_greedy"] == out["graph_greedy"]).float().mean()), 4)
         rec["graph_greedy_over_default"] = round(med["graph_greedy"] / med["default_greedy"], 3)
         rec["graph_sampled_over_default_top_k"] = round(med["graph_sampled"] / med["default_top_k"], 3)
         rec["greedy_tokens_equal_fraction_graph_vs_default"] = round(
