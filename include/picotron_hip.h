@@ -559,6 +559,47 @@ int64_t pico_decode_linear_split_k(int64_t n, int64_t k, int epilogue);
 int64_t pico_decode_linear_workspace_bytes(int64_t m, int64_t n, int64_t k, int epilogue, int64_t split_k);
 int pico_decode_linear(const pico_decode_linear_args* args, void* stream);
 
+/* ---- Generation: FP8 (OCP e4m3) weight-only skinny linear and its row quantiser ----
+ * A quantised weight is codes [n, k], one e4m3 byte each (finite codes only: never 0x7f / 0xff), plus scale [n] fp32,
+ *   one per output row: element (n, k) has the value scale[n] * e4m3(codes[n, k]).
+ * pico_quantize_rows_fp8: w [n, k] bf16 (finite), row stride ldw elements -> codes with row stride ldc bytes, and
+ *   scale. scale[n] = absmax(row n) / 448, a correctly rounded fp32 division (a row of zeros: 1); code = RNE to e4m3
+ *   of clamp(float(w) / scale, -448, 448), again a correctly rounded division: plain fp32 arithmetic reproduces it
+ *   bit for bit. k, ldw and ldc multiples of 8, w 16-byte and codes 8-byte aligned. n == 0 is a no-op. Timed under
+ *   PICO_K_CAST.
+ * pico_decode_linear_fp8: pico_decode_linear's contract with two changes. acc[m, n] = sum_k h[m, k] *
+ *   e4m3(weight[n, k]) in fp32 on the matrix pipe (every product exact), and scale[n] * acc, one fp32 multiply taken
+ *   after the wave reduction (after the slice sum in the finishing launch), takes acc's place in every epilogue:
+ *   PICO_DL_BF16 y = bf16(scale acc); PICO_DL_F32 y = float(bf16(scale acc)); PICO_DL_SWIGLU g = bf16(scale_g
+ *   acc_g), u = bf16(scale_u acc_u), then pico_swiglu_fwd's arithmetic. Split-K partials are written unscaled.
+ *   weight is bytes, ldw its row stride in bytes (a multiple of 16); weight_scale [n] fp32, 16-byte aligned; k a
+ *   multiple of 64. Everything else (m in 1..16, the norm prologue and the residual_out rule, the other strides and
+ *   alignments, split_k, determinism, row independence) is pico_decode_linear's.
+ * pico_decode_linear_fp8_plan: plan[0..3] = column blocks, split_k, k_slice, workspace bytes for the shape and
+ *   split_k (<= 0: the host rule on n, k, the epilogue and the CU count; m enters the workspace size only). cus <= 0:
+ *   the current device's (256 without one). PICO_EINVAL for a shape or split the kernel refuses (a slice may hold at
+ *   most 2048 columns). Timed under PICO_K_DECODE_LINEAR. */
+typedef struct pico_decode_linear_fp8_args {
+  const void* x;
+  const void* weight;
+  const float* weight_scale;
+  void* y;
+  const void* norm_weight;
+  const void* residual;
+  void* residual_out;
+  void* workspace;
+  int64_t ldx, ldw, ldy, ldr, ldro;
+  int64_t m, n, k;
+  int64_t split_k;
+  float eps;
+  int epilogue;
+} pico_decode_linear_fp8_args;
+int pico_quantize_rows_fp8(const void* w, int64_t ldw, void* codes, int64_t ldc, float* scale, int64_t n, int64_t k,
+                           void* stream);
+int64_t pico_decode_linear_fp8_args_size(void);
+int pico_decode_linear_fp8_plan(int64_t m, int64_t n, int64_t k, int epilogue, int64_t split_k, int cus, int64_t* plan);
+int pico_decode_linear_fp8(const pico_decode_linear_fp8_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

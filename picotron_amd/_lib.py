@@ -71,6 +71,17 @@ class DecodeLinearArgs(ctypes.Structure):
     ]
 
 
+class DecodeLinearFp8Args(ctypes.Structure):
+    """Mirror of `pico_decode_linear_fp8_args`."""
+    _fields_ = [
+        ("x", c_vp), ("weight", c_vp), ("weight_scale", c_vp), ("y", c_vp), ("norm_weight", c_vp), ("residual", c_vp),
+        ("residual_out", c_vp), ("workspace", c_vp),
+        ("ldx", c_i64), ("ldw", c_i64), ("ldy", c_i64), ("ldr", c_i64), ("ldro", c_i64),
+        ("m", c_i64), ("n", c_i64), ("k", c_i64), ("split_k", c_i64),
+        ("eps", ctypes.c_float), ("epilogue", ctypes.c_int),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "pico_abi_version": (ctypes.c_int, []),
@@ -149,6 +160,11 @@ _SIGNATURES = {
     "pico_decode_linear_split_k": (c_i64, [c_i64, c_i64, ctypes.c_int]),
     "pico_decode_linear_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, ctypes.c_int, c_i64]),
     "pico_decode_linear": (ctypes.c_int, [ctypes.POINTER(DecodeLinearArgs), c_vp]),
+    "pico_quantize_rows_fp8": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    "pico_decode_linear_fp8_args_size": (c_i64, []),
+    "pico_decode_linear_fp8_plan": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, c_i64, ctypes.c_int,
+                                                   ctypes.POINTER(c_i64)]),
+    "pico_decode_linear_fp8": (ctypes.c_int, [ctypes.POINTER(DecodeLinearFp8Args), c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

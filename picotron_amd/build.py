@@ -40,6 +40,8 @@ FILE_FLAGS = {
     # scratch either way). -fno-slp-vectorize would do as well for today's code; the target feature also covers what
     # later passes may form. Not measured apart for this kernel.
     "decode_linear.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # the same prologue and epilogues, and the quantiser's clamp: no packed fp32 VALU here either
+    "decode_linear_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -327,14 +327,74 @@ def _check_skinny(model, B):
                          f"(ops.decode_linear): {', '.join(bad)}")
 
 
-def _layers_skinny(model, plan, x, pos, attend):
+class DecodeWeights:
+    """The decode projections of a model as FP8 weights (ops.Fp8Weight: e4m3 codes, one fp32 scale per output row):
+    per layer the stacked q|k|v, out, the stacked gate|up and down, plus the LM head. Norm weights and the embedding
+    are not part of it: they stay the model's bf16 parameters. A snapshot: it holds what the model's weights were
+    when quantize_decode_weights ran and does not follow an optimizer step or a load_state_dict; quantise again."""
+
+    def __init__(self, layers, head):
+        self.layers, self.head = layers, head
+
+    def shapes(self):
+        return [tuple(tuple(w.shape) for w in layer) for layer in self.layers] + [tuple(self.head.shape)]
+
+
+def _decode_shapes(model):
+    """DecodeWeights.shapes() as the model's parameters have them."""
+    out = []
+    for layer in model.decoder_layers:
+        a, f = layer.attention, layer.mlp
+        K = a.q_proj.weight.shape[1]
+        qkv = a.q_proj.weight.shape[0] + a.k_proj.weight.shape[0] + a.v_proj.weight.shape[0]
+        out.append(((qkv, K), tuple(a.out_proj.weight.shape), (2 * f.gate_proj.weight.shape[0], K),
+                    tuple(f.down_proj.weight.shape)))
+    return out + [tuple(model.final_proj.weight.shape)]
+
+
+@torch.no_grad()
+def quantize_decode_weights(model):
+    """DecodeWeights of `model`: every decode projection quantised once by ops.quantize_weight_fp8 (the stacked
+    q|k|v and gate|up as the stacked views ops.stacked_weight gives, without a bf16 copy). Pass the result as
+    decode_step / generate's decode_weights (with skinny_linear=True). It is a snapshot of the weights as they are
+    now, half the bytes of the bf16 projections plus 4 bytes per output row."""
+    _check_model(model)
+    q = ops.quantize_weight_fp8
+    layers = []
+    for layer in model.decoder_layers:
+        a, f = layer.attention, layer.mlp
+        layers.append((q((a.q_proj.weight, a.k_proj.weight, a.v_proj.weight)), q(a.out_proj.weight),
+                       q((f.gate_proj.weight, f.up_proj.weight)), q(f.down_proj.weight)))
+    return DecodeWeights(layers, q(model.final_proj.weight))
+
+
+def _check_decode_weights(model, w, skinny_linear):
+    """decode_weights is refused without skinny_linear, for another model's shapes, and where ops.decode_linear
+    would refuse a projection (an Fp8Weight needs K to be a multiple of 64)."""
+    if not skinny_linear:
+        raise ValueError("generate: decode_weights belongs to skinny_linear=True (the FP8 weights are read by "
+                         "ops.decode_linear alone)")
+    if not isinstance(w, DecodeWeights) or w.shapes() != _decode_shapes(model):
+        raise ValueError("generate: decode_weights does not fit this model (quantize_decode_weights(model) makes it)")
+    *layers, head = w.shapes()
+    bad = sorted({k for layer in layers for _, k in layer} | {head[1]})
+    bad = [f"K = {k}" for k in bad if k % 64]
+    if bad:
+        raise ValueError("generate: decode_weights needs every projection's K to be a multiple of 64 "
+                         f"(ops.decode_linear with an Fp8Weight): {', '.join(bad)}")
+
+
+def _layers_skinny(model, plan, x, pos, attend, decode_weights=None):
     """_layers for a decode step (x [B <= 16, 1, hidden]) on ops.decode_linear: each norm runs inside the projection
     after it and the SwiGLU inside gate|up, with _layers' rounding points. Per layer: norm + q|k|v, the cache
-    append, the decode attention, the out projection, norm + gate|up + SwiGLU, the down projection."""
+    append, the decode attention, the out projection, norm + gate|up + SwiGLU, the down projection. decode_weights:
+    the four projections read its Fp8Weights instead of the plan's bf16 weights."""
     Hq, Hkv = model.num_heads, model.num_key_values
     B = x.shape[0]
     delta, residual = x.view(B, -1), None
-    for w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc in plan:
+    for i, (w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc) in enumerate(plan):
+        if decode_weights is not None:
+            w_qkv, w_out, w_gu, w_down = decode_weights.layers[i]
         qkv, residual = ops.decode_linear(delta, w_qkv, norm_weight=w_in, eps=eps_in, residual=residual)
         q = kv_cache_append(qkv.view(B, 1, -1), cos, sin, pos, kc, vc, Hq, Hkv)
         o = ops.decode_linear(attend(q, kc, vc).view(B, -1), w_out)
@@ -343,8 +403,9 @@ def _layers_skinny(model, plan, x, pos, attend):
     return delta, residual
 
 
-def _head_skinny(model, delta, residual):
-    return ops.decode_linear(delta, model.final_proj.weight, norm_weight=model.final_norm.weight,
+def _head_skinny(model, delta, residual, decode_weights=None):
+    w = model.final_proj.weight if decode_weights is None else decode_weights.head
+    return ops.decode_linear(delta, w, norm_weight=model.final_norm.weight,
                              eps=model.final_norm.eps, residual=residual, out_dtype=torch.float32)[0]
 
 
@@ -393,16 +454,23 @@ def prefill(model, input_ids, cache, prompt_lens=None):
 
 
 @torch.no_grad()
-def decode_step(model, tokens, cache, skinny_linear=False):
+def decode_step(model, tokens, cache, skinny_linear=False, decode_weights=None):
     """One token per row: tokens int64 [B] -> fp32 logits [B, V] of the next token; the cache grows by one. No host
     synchronisation: the positions are cache.lens on the device. A row whose cache is full writes nothing and
     attends to the full cache (generate() refuses lengths that would get there).
 
     skinny_linear=True (B <= 16): the projections run on ops.decode_linear, one pass over each weight with the norm
-    before it and the SwiGLU after it in the same launch, instead of F.linear and the row-wise kernels beside it."""
+    before it and the SwiGLU after it in the same launch, instead of F.linear and the row-wise kernels beside it.
+
+    decode_weights (quantize_decode_weights(model); with skinny_linear=True only, refused otherwise, for another
+    model's shapes, or where a projection's K is not a multiple of 64): the projections stream FP8 weights, half the
+    bytes. Prefill does not take it: the prompt's K/V come from the bf16 weights, the generated tokens' from the
+    FP8 ones."""
     if tokens.dim() != 1:
         raise ValueError("decode_step: tokens must be [batch]")
     B = tokens.shape[0]
+    if decode_weights is not None:
+        _check_decode_weights(model, decode_weights, skinny_linear)
     if skinny_linear:
         _check_skinny(model, B)
     plan = cache._plan if isinstance(cache, KVCache) and cache._plan_model is model else None
@@ -420,7 +488,8 @@ def decode_step(model, tokens, cache, skinny_linear=False):
 
     x = torch.nn.functional.embedding(tokens.view(B, 1), model.embedding.weight)
     if skinny_linear:
-        logits = _head_skinny(model, *_layers_skinny(model, plan, x, cache.lens, attend))
+        logits = _head_skinny(model, *_layers_skinny(model, plan, x, cache.lens, attend, decode_weights),
+                              decode_weights)
     else:
         delta, residual = _layers(model, plan, x, cache.lens, attend)
         logits = _head(model, delta[:, 0], residual[:, 0] if residual is not None else None)
@@ -674,7 +743,7 @@ def _generate_cache(model, input_ids, max_new_tokens, cache):
 
 
 def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p, eos_token_id,
-                    pad_token_id, seed, return_logits, cache, graph, skinny_linear=False):
+                    pad_token_id, seed, return_logits, cache, graph, skinny_linear=False, decode_weights=None):
     cache = _generate_cache(model, input_ids, max_new_tokens, cache)
     B, N = input_ids.shape[0], max_new_tokens
     dev = input_ids.device
@@ -688,7 +757,7 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
         state = SamplerState(B, dev, out=torch.empty((B, N), dtype=torch.int64, device=dev), **settings)
         sample_tokens(logits, state)
         for step in range(1, N):
-            logits = decode_step(model, state.tokens, cache, skinny_linear)
+            logits = decode_step(model, state.tokens, cache, skinny_linear, decode_weights)
             if keep is not None:
                 keep[:, step] = logits
             sample_tokens(logits, state)
@@ -696,6 +765,8 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
 
     from .train import _capturing
     key = _graph_key(model, cache) + (bool(skinny_linear),)  # a graph replays the route it was captured with
+    if decode_weights is not None:  # ... and the FP8 weights: the held graph keeps the object, so its id stays its own
+        key += (id(decode_weights),)
     held = cache._graph if cache._graph is not None and cache._graph.fits(model, key) else None
     if held is not None:
         state = held.state.set(**settings).reset()
@@ -709,7 +780,7 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
         side = _capture_stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            logits = decode_step(model, state.tokens, cache, skinny_linear)
+            logits = decode_step(model, state.tokens, cache, skinny_linear, decode_weights)
             sample_tokens(logits, state)
         torch.cuda.current_stream(dev).wait_stream(side)
         if keep is not None:
@@ -717,13 +788,14 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
             logits.record_stream(torch.cuda.current_stream(dev))  # allocated on `side`, read here
         g = torch.cuda.CUDAGraph()
         with _capturing(g):
-            static_logits = decode_step(model, state.tokens, cache, skinny_linear)
+            static_logits = decode_step(model, state.tokens, cache, skinny_linear, decode_weights)
             sample_tokens(static_logits, state)
         # the workspace the two passes above used on this stream (decode attention's and decode_linear's partials):
         # the graph points into it, so the graph holds it; a later, larger request replaces the dict's entry, not
         # this tensor
         workspace = _WORKSPACES[(static_logits.device, side.cuda_stream)]
         held = cache._graph = _DecodeGraph(key + (workspace.data_ptr(),), model, g, state, static_logits, workspace)
+        held.decode_weights = decode_weights
         cache.graph_captures += 1
         first = 2
     for step in range(first, N):
@@ -737,7 +809,7 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
 @torch.no_grad()
 def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0, top_k=None, eos_token_id=None,
              pad_token_id=0, generator=None, return_logits=False, cache=None, top_p=None, seed=None, graph=False,
-             skinny_linear=False):
+             skinny_linear=False, decode_weights=None):
     """Sample max_new_tokens tokens per row after the (right-padded) prompts: int64 [B, max_new_tokens], and with
     return_logits the fp32 [B, max_new_tokens, V] each token was drawn from. One prefill, then max_new_tokens - 1
     decode steps. A row that has emitted eos_token_id yields pad_token_id from then on (masked on the device; no
@@ -751,7 +823,14 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
     model and batch, whatever their settings. generator= belongs to the default path only.
 
     skinny_linear=True (batch <= 16, refused beyond) runs every decode step's projections on ops.decode_linear
-    (decode_step); the prefill is untouched. A captured graph is captured with, and keyed by, the setting."""
+    (decode_step); the prefill is untouched. A captured graph is captured with, and keyed by, the setting.
+
+    decode_weights (quantize_decode_weights(model), with skinny_linear=True only): the decode steps' projections
+    stream FP8 (e4m3) weights, half the bytes of the bf16 ones. Prefill keeps running on the bf16 weights and the
+    training kernels: the prompt's K/V come from the bf16 weights, the generated tokens' from the FP8 ones. The
+    object is a snapshot of the model's weights; a captured graph is keyed by its identity as well."""
+    if decode_weights is not None:
+        _check_decode_weights(model, decode_weights, skinny_linear)
     if skinny_linear:
         _check_skinny(model, input_ids.shape[0] if input_ids.dim() == 2 else 1)
     if top_p is not None or seed is not None or graph:
@@ -759,7 +838,8 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
             raise ValueError("generate: generator= cannot be combined with top_p / seed / graph (the fused sampler "
                              "draws from its seed)")
         return _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p,
-                               eos_token_id, pad_token_id, seed, return_logits, cache, graph, skinny_linear)
+                               eos_token_id, pad_token_id, seed, return_logits, cache, graph, skinny_linear,
+                               decode_weights)
     cache = _generate_cache(model, input_ids, max_new_tokens, cache)
     B = input_ids.shape[0]
     dev = input_ids.device
@@ -770,7 +850,7 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
     logits = prefill(model, input_ids, cache, prompt_lens)
     for step in range(max_new_tokens):
         if step:
-            logits = decode_step(model, tok, cache, skinny_linear)
+            logits = decode_step(model, tok, cache, skinny_linear, decode_weights)
         if keep is not None:
             keep[:, step] = logits
         tok = sample_next(logits, temperature, top_k, generator)

@@ -1425,9 +1425,10 @@ def _attention_bwd_into(dout, q, k, v, o, lse, softmax_scale, causal, dq, dk, dv
 DECODE_LINEAR_MAX_ROWS = 16  # csrc/decode_linear_plan.h DL_MAX_M
 
 
-def _decode_linear_reference(x, weight, norm_weight, eps, residual, swiglu, out_dtype):
+def _decode_linear_reference(x, weight, norm_weight, eps, residual, swiglu, out_dtype, scale=None):
     """pico_decode_linear's contract in plain torch: fp32 arithmetic (fp64 for fp64 inputs), a bf16 rounding at each
-    of the kernel's rounding points."""
+    of the kernel's rounding points. scale [N] (pico_decode_linear_fp8: weight holds the e4m3 codes): one multiply
+    of the accumulator before its rounding."""
     ct = torch.float64 if x.dtype == torch.float64 else torch.float32
 
     def rnd(t):
@@ -1440,7 +1441,8 @@ def _decode_linear_reference(x, weight, norm_weight, eps, residual, swiglu, out_
             res_out = h.to(_BF16)
         rstd = torch.rsqrt(h.pow(2).mean(-1, keepdim=True) + eps)
         h = rnd(h * rstd * norm_weight.to(ct))
-    acc = rnd(h @ weight.to(ct).t())
+    acc = h @ weight.to(ct).t()
+    acc = rnd(acc if scale is None else acc * scale.to(ct))
     if swiglu:
         inter = weight.shape[0] // 2
         g, u = acc[:, :inter], acc[:, inter:]
@@ -1462,7 +1464,13 @@ def decode_linear(x, weight, *, norm_weight=None, eps=None, residual=None, swigl
     given split_k and a row does not depend on the other rows.
 
     HIP bf16 tensors take the kernel; CPU tensors, and tensors of another float dtype, the plain-torch restatement
-    with the same rounding points. M > 16 or a shape the kernel does not take raises ValueError."""
+    with the same rounding points. M > 16 or a shape the kernel does not take raises ValueError.
+
+    weight may be an Fp8Weight (ops.quantize_weight_fp8): e4m3 codes and one fp32 scale per output row. The products
+    h * e4m3(code) are accumulated in fp32 and scale[n] * acc, one fp32 multiply, takes acc's place in every
+    epilogue (pico_decode_linear_fp8); K must then be a multiple of 64. Every other argument keeps its meaning."""
+    if isinstance(weight, Fp8Weight):
+        return _decode_linear_fp8(x, weight, norm_weight, eps, residual, swiglu, out_dtype, split_k)
     if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
         raise ValueError(f"decode_linear: x {tuple(x.shape)} and weight {tuple(weight.shape)} must be [M, K] and [N, K]")
     M, K = x.shape
@@ -1514,6 +1522,119 @@ def decode_linear(x, weight, *, norm_weight=None, eps=None, residual=None, swigl
     a.ldr, a.ldro = (residual.stride(0), K) if residual is not None else (0, 0)
     a.m, a.n, a.k, a.split_k, a.eps, a.epilogue = M, N, K, sk, eps, epi
     _lib.check(lib.pico_decode_linear(ctypes.byref(a), _lib.stream_of(x)), "pico_decode_linear")
+    if norm_weight is None:
+        return y
+    return y, (res_out if res_out is not None else x)
+
+
+# --------------------------------------------------------------------------------------------
+# FP8 (OCP e4m3) weight-only skinny linear: csrc/decode_linear_fp8.hip
+# --------------------------------------------------------------------------------------------
+_E4M3 = torch.float8_e4m3fn
+E4M3_MAX = 448.0
+
+
+class Fp8Weight:
+    """A row-quantised weight: codes [N, K] torch.float8_e4m3fn (finite codes only) and scale [N] fp32; element
+    (n, k) has the value scale[n] * e4m3(codes[n, k]). Rows of two Fp8Weights concatenate into the stacked matrix's."""
+    __slots__ = ("codes", "scale")
+
+    def __init__(self, codes, scale):
+        if codes.dim() != 2 or codes.dtype != _E4M3 or scale.shape != (codes.shape[0],) or \
+                scale.dtype != torch.float32 or scale.device != codes.device:
+            raise ValueError("Fp8Weight: codes [N, K] float8_e4m3fn and scale [N] float32 on one device")
+        self.codes, self.scale = codes, scale
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+    def dequantize(self, dtype=torch.float32):
+        """scale * e4m3(codes), exact in fp32 (a 4-bit significand times a 24-bit one), rounded once to `dtype`."""
+        return (self.codes.float() * self.scale[:, None]).to(dtype)
+
+
+def quantize_weight_fp8(weight):
+    """Fp8Weight of a bf16 weight [N, K] (or of the tuple ops.stacked_weight takes: the stacked view is quantised,
+    no bf16 copy), one scale per row: scale = absmax / 448 (fp32 division; a row of zeros: 1), code = RNE to e4m3 of
+    clamp(float(w) / scale, -448, 448). HIP tensors take pico_quantize_rows_fp8 (K a multiple of 8), CPU tensors the
+    same arithmetic in plain torch, bit for bit. The weight must be finite."""
+    w = stacked_weight(tuple(weight)) if isinstance(weight, (tuple, list)) else weight.detach()
+    if w.dim() != 2 or w.dtype != _BF16 or w.stride(1) != 1:
+        raise ValueError("quantize_weight_fp8: weight must be a bf16 [N, K] matrix with unit last stride")
+    N, K = w.shape
+    if w.device.type == "cpu":
+        a = w.float().abs().amax(1)
+        scale = torch.where(a == 0, torch.ones_like(a), a / E4M3_MAX)
+        return Fp8Weight((w.float() / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(_E4M3), scale)
+    _need(w, "weight")
+    if K % 8 or w.stride(0) % 8:
+        raise ValueError(f"quantize_weight_fp8: K = {K} and the row stride must be multiples of 8")
+    codes = torch.empty((N, K), dtype=_E4M3, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    _lib.check(_lib.load().pico_quantize_rows_fp8(w.data_ptr(), w.stride(0), codes.data_ptr(), K, scale.data_ptr(),
+                                                  N, K, _lib.stream_of(w)), "pico_quantize_rows_fp8")
+    return Fp8Weight(codes, scale)
+
+
+def _decode_linear_fp8(x, weight, norm_weight, eps, residual, swiglu, out_dtype, split_k):
+    """ops.decode_linear for an Fp8Weight: the same checks, then pico_decode_linear_fp8 or the restatement."""
+    codes, scale = weight.codes, weight.scale
+    if x.dim() != 2 or x.shape[1] != codes.shape[1]:
+        raise ValueError(f"decode_linear: x {tuple(x.shape)} and weight {tuple(codes.shape)} must be [M, K] and [N, K]")
+    M, K = x.shape
+    N = codes.shape[0]
+    if not 1 <= M <= DECODE_LINEAR_MAX_ROWS:
+        raise ValueError(f"decode_linear: {M} rows; 1..{DECODE_LINEAR_MAX_ROWS} are supported (a decode step's batch)")
+    if K % 64 or N % (16 if swiglu else 8):
+        raise ValueError(f"decode_linear: with an Fp8Weight K = {K} must be a multiple of 64 and N = {N} of "
+                         f"{16 if swiglu else 8}")
+    out_dtype = _BF16 if out_dtype is None else out_dtype
+    if out_dtype not in (_BF16, torch.float32) or (swiglu and out_dtype != _BF16):
+        raise ValueError("decode_linear: out_dtype is bfloat16, or float32 without swiglu")
+    if norm_weight is None and (residual is not None or eps is not None):
+        raise ValueError("decode_linear: residual / eps belong to the norm prologue (norm_weight is None)")
+    if norm_weight is not None and (norm_weight.shape != (K,) or not norm_weight.is_contiguous()):
+        raise ValueError(f"decode_linear: norm_weight must be a contiguous [{K}] tensor")
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("decode_linear: residual must have x's shape")
+    for t, n in ((x, "x"), (residual, "residual")):
+        if t is not None and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < K):
+            raise ValueError(f"decode_linear: {n} needs unit last stride and a row stride that is a multiple of 8")
+    if codes.stride(1) != 1 or codes.stride(0) % 16 or not scale.is_contiguous() or codes.device != x.device:
+        raise ValueError("decode_linear: the Fp8Weight's codes need unit last stride and a row stride that is a "
+                         "multiple of 16 bytes, a contiguous scale, and x's device")
+    if split_k is not None and int(split_k) <= 0:
+        raise ValueError("decode_linear: split_k must be positive")
+    eps = 1e-5 if eps is None else float(eps)
+    if x.device.type == "cpu" or x.dtype != _BF16:
+        y, res_out = _decode_linear_reference(x, codes, norm_weight, eps, residual, swiglu, out_dtype, scale=scale)
+        if norm_weight is None:
+            return y
+        return y, (res_out if res_out is not None else x)
+    from .generate import _workspace
+    for t, n in ((x, "x"), (norm_weight, "norm_weight"), (residual, "residual")):
+        if t is not None:
+            _need(t, n)
+    lib = _lib.load()
+    epi = _lib.DL_SWIGLU if swiglu else (_lib.DL_F32 if out_dtype == torch.float32 else _lib.DL_BF16)
+    sk = 0 if split_k is None else int(split_k)
+    plan = (ctypes.c_int64 * 4)()
+    if lib.pico_decode_linear_fp8_plan(M, N, K, epi, sk, 0, plan):
+        raise ValueError("decode_linear: " + lib.pico_last_error().decode(errors="replace"))
+    ws = _workspace(x.device, plan[3]) if plan[3] else None
+    y = torch.empty((M, N // 2 if swiglu else N), dtype=out_dtype, device=x.device)
+    res_out = torch.empty((M, K), dtype=_BF16, device=x.device) if residual is not None else None
+    a = _lib.DecodeLinearFp8Args()
+    a.x, a.weight, a.weight_scale, a.y = x.data_ptr(), codes.data_ptr(), scale.data_ptr(), y.data_ptr()
+    a.norm_weight = norm_weight.data_ptr() if norm_weight is not None else None
+    a.residual = residual.data_ptr() if residual is not None else None
+    a.residual_out = res_out.data_ptr() if res_out is not None else None
+    a.workspace = ws.data_ptr() if ws is not None else None
+    a.ldx, a.ldw, a.ldy = x.stride(0), codes.stride(0), y.stride(0)
+    a.ldr, a.ldro = (residual.stride(0), K) if residual is not None else (0, 0)
+    a.m, a.n, a.k, a.split_k, a.eps, a.epilogue = M, N, K, sk, eps, epi
+    _lib.check(lib.pico_decode_linear_fp8(ctypes.byref(a), _lib.stream_of(x)), "pico_decode_linear_fp8")
     if norm_weight is None:
         return y
     return y, (res_out if res_out is not None else x)

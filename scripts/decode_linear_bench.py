@@ -11,11 +11,13 @@ of a peak. Kernel times come from a kernel trace:
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/decode_linear_bench.py trace
   python scripts/decode_linear_bench.py table --trace DIR/.../*_kernel_trace.csv [--out profiles/...jsonl]
 
-`trace` warms every form up, then runs, per shape and M, a marker launch (pico_scale_f32), --iters decode_linear
-calls, a marker, --iters F.linear calls (the GEMM alone: what hipBLASLt launches for the shape); nothing else runs
-on the device in between. `table` cuts the trace at the markers and reports, per shape and M, the median kernel time
-per call of the stream kernel, of the finishing launch and of hipBLASLt's kernels, with the weight's bytes over the
-stream + finish time as a share of the HBM peak.
+`trace` quantises every weight of the ring once (ops.quantize_weight_fp8), warms every form up, then runs, per shape
+and M, a marker launch (pico_scale_f32), --iters decode_linear calls, a marker, --iters F.linear calls (the GEMM
+alone: what hipBLASLt launches for the shape), a marker, --iters decode_linear calls on the Fp8Weights; nothing else
+runs on the device in between. `table` cuts the trace at the markers and reports, per shape and M, the median kernel
+time per call of the stream kernel, of the finishing launch and of hipBLASLt's kernels, with the weight's bytes over
+the stream + finish time as a share of the HBM peak; the same for the FP8 kernels (share on the FP8 bytes, N K), and
+the quantiser's time per matrix.
 
 Usage: python scripts/decode_linear_bench.py [calls|trace|table] [--out FILE] [--iters 40] [--rounds 3] [--trace CSV]
 """
@@ -124,6 +126,18 @@ def trace(args):
     def gemm(c, i):
         torch.nn.functional.linear(xs[(c[0], c[6])][0], c[7][i % len(c[7])])
 
+    # every copy of the ring quantised once (pico_quantize_rows_fp8: the trace holds one launch per matrix)
+    q8 = {}
+    for c in cases:
+        if c[0] not in q8:
+            q8[c[0]] = [ops.quantize_weight_fp8(w) for w in c[7]]
+
+    def fp8(c, i):
+        name, N, K, norm, swiglu, f32, M, ws = c
+        x, res = xs[(name, M)]
+        kw = dict(norm_weight=gamma[K], eps=1e-5, residual=res) if norm else {}
+        ops.decode_linear(x, q8[name][i % len(ws)], swiglu=swiglu, out_dtype=torch.float32 if f32 else None, **kw)
+
     def marker():
         _lib.check(lib.pico_scale_f32(_lib.ptr(mark), mark.numel(), 2.0, _lib.stream_of(mark)), "pico_scale_f32")
 
@@ -132,9 +146,10 @@ def trace(args):
             for i in range(3):
                 skinny(c, i)
                 gemm(c, i)
+                fp8(c, i)
         torch.cuda.synchronize()
         for c in cases:
-            for fn in (skinny, gemm):
+            for fn in (skinny, gemm, fp8):
                 marker()
                 for i in range(args.iters):
                     fn(c, i)
@@ -155,10 +170,20 @@ def table(args):
             cur.append((r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
     segs = segs[:-1]  # the closing marker opens nothing
     combos = [(s[0], s[1], s[2], M) for s in SHAPES for M in (1, 8)]
-    assert len(segs) == 2 * len(combos), (len(segs), len(combos))
+    assert len(segs) == 3 * len(combos), (len(segs), len(combos))
     med = lambda v: sorted(v)[len(v) // 2] if v else 0.0
+    quant = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows
+             if "quantize_rows_fp8" in r["Kernel_Name"]]
+    quant_us = {}
+    for name, N, K, *_ in SHAPES:  # one launch per matrix of the ring, shape after shape
+        copies = max(2, RING_BYTES // (N * K * 2) + 1)
+        quant_us[name], quant = round(med(quant[:copies]), 2), quant[copies:]
     for i, (name, N, K, M) in enumerate(combos):
-        ours, theirs = segs[2 * i], segs[2 * i + 1]
+        ours, theirs, eight = segs[3 * i], segs[3 * i + 1], segs[3 * i + 2]
+        stream8 = [t for n, t in eight if "decode_linear_fp8_kernel" in n]
+        finish8 = [t for n, t in eight if "decode_linear_fp8_finish" in n]
+        assert len(stream8) + len(finish8) == len(eight) and len(stream8) == args.iters, (name, M, len(eight))
+        total8 = med(stream8) + med(finish8)
         stream = [t for n, t in ours if "decode_linear_kernel" in n]
         finish = [t for n, t in ours if "decode_linear_finish" in n]
         assert len(stream) + len(finish) == len(ours) and len(stream) == args.iters, (name, M, len(ours))
@@ -171,7 +196,10 @@ def table(args):
                "stream_us": round(med(stream), 2), "finish_us": round(med(finish), 2), "decode_linear_us": round(total, 2),
                "decode_linear_hbm_share": share(total), "hipblaslt_us": round(gemm_us, 2),
                "hipblaslt_kernels_per_call": per_call, "hipblaslt_hbm_share": share(gemm_us),
-               "hipblaslt_kernel": theirs[0][0][:80]}
+               "hipblaslt_kernel": theirs[0][0][:80],
+               "fp8_stream_us": round(med(stream8), 2), "fp8_finish_us": round(med(finish8), 2),
+               "fp8_us": round(total8, 2), "fp8_hbm_share": round(share(total8) / 2, 3),  # on the FP8 bytes: N K
+               "fp8_over_bf16": round(total8 / total, 3), "quantize_us": quant_us[name]}
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:

@@ -130,18 +130,20 @@ def e2e(args):
     weights = sum(p.numel() for layer in model.decoder_layers for p in layer.parameters() if p.dim() == 2)
     weights += model.final_proj.weight.numel()
     floor_ms = 1e3 * weights * 2 / (HBM_PEAK_GBS * 1e9)
+    fp8 = G.quantize_decode_weights(model)  # one byte per weight: half the floor
     P, N = 128, 128
     sampled = dict(temperature=0.8, top_k=50, top_p=0.9, seed=1)
     for B in (1, 8):
         prompt = torch.randint(0, cfg.vocab_size, (B, P), generator=torch.Generator().manual_seed(B)).to(dev)
         cache = G.KVCache(model, B, P + N)
         skinny_cache = G.KVCache(model, B, P + N)  # a cache holds one captured graph: the skinny route keeps its own
+        fp8_cache = G.KVCache(model, B, P + N)
         out = {}
 
         def run(name, **kw):
             def fn():
-                out[name] = G.generate(model, prompt, N, cache=skinny_cache if kw.get("skinny_linear") else cache,
-                                       **kw)
+                c = fp8_cache if "decode_weights" in kw else skinny_cache if kw.get("skinny_linear") else cache
+                out[name] = G.generate(model, prompt, N, cache=c, **kw)
             return fn
 
         def prefill_only():
@@ -152,11 +154,14 @@ def e2e(args):
                  "fused_eager_greedy": run("fused_eager_greedy", seed=1),
                  "graph_greedy": run("graph_greedy", graph=True),
                  "skinny_graph_greedy": run("skinny_graph_greedy", graph=True, skinny_linear=True),
+                 "fp8_graph_greedy": run("fp8_graph_greedy", graph=True, skinny_linear=True, decode_weights=fp8),
                  "default_top_k": run("default_top_k", temperature=0.8, top_k=50,
                                       generator=torch.Generator(dev).manual_seed(1)),
                  "fused_eager_sampled": run("fused_eager_sampled", **sampled),
                  "graph_sampled": run("graph_sampled", graph=True, **sampled),
                  "skinny_graph_sampled": run("skinny_graph_sampled", graph=True, skinny_linear=True, **sampled),
+                 "fp8_graph_sampled": run("fp8_graph_sampled", graph=True, skinny_linear=True, decode_weights=fp8,
+                                          **sampled),
                  "prefill": prefill_only}
         for name, fn in forms.items():  # one warm pass: code objects, GEMM algorithms, the capture
             _clock_ms(fn)
@@ -179,6 +184,11 @@ def e2e(args):
             a, b = ms["skinny_graph_" + kind], ms["graph_" + kind]
             rec[f"skinny_over_graph_{kind}"] = round(med["skinny_graph_" + kind] / med["graph_" + kind], 3)
             rec[f"skinny_vs_graph_{kind}_spread_ms"] = round(max(max(a) - min(a), max(b) - min(b)), 1)
+            c = ms["fp8_graph_" + kind]  # the FP8 weights against the bf16 skinny route, and against their own floor
+            rec[f"fp8_over_skinny_{kind}"] = round(med["fp8_graph_" + kind] / med["skinny_graph_" + kind], 3)
+            rec[f"fp8_vs_skinny_{kind}_spread_ms"] = round(max(max(a) - min(a), max(c) - min(c)), 1)
+            rec[f"fp8_graph_{kind}_step_over_fp8_floor"] = round(
+                (med["fp8_graph_" + kind] - med["prefill"]) / (N - 1) / (floor_ms / 2), 2)
         rec["skinny_greedy_tokens_equal_fraction_vs_graph"] = round(
             float((out["skinny_graph_greedy"] == out["graph_greedy"]).float().mean()), 4)
         rec["graph_greedy_over_default"] = round(med["graph_greedy"] / med["default_greedy"], 3)
