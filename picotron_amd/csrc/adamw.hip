@@ -27,10 +27,18 @@ struct AdamHyper {
   float step_size;
 };
 
+// The fp32 value of x, opaque to the compiler (no instruction). adam_elem's moments are double expressions rounded to
+// fp32 and, in the bf16 forms, rounded again to bf16 by the store. Without the pin the scalar loop rounded the double
+// to bf16 in one step while the vector loop rounded twice (tests/test_optim_kernels_gpu.py: about 1 % of a scalar
+// tensor's exp_avg, wherever 0.9 m + 0.1 g is a bf16 tie), against "the same values either way".
+PICO_DEV void pin_f32(float& x) { asm("" : "+v"(x)); }
+
 PICO_DEV void adam_elem(float& p, float g, float& m, float& v, const AdamHyper& h) {
   p -= h.lr_wd * p;
   m = h.b1 * m + (1 - h.b1) * g;
   v = h.b2 * v + (1 - h.b2) * g * g;
+  pin_f32(m);
+  pin_f32(v);
   const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
   p -= h.step_size * m / denom;
 }
