@@ -600,6 +600,36 @@ int64_t pico_decode_linear_fp8_args_size(void);
 int pico_decode_linear_fp8_plan(int64_t m, int64_t n, int64_t k, int epilogue, int64_t split_k, int cus, int64_t* plan);
 int pico_decode_linear_fp8(const pico_decode_linear_fp8_args* args, void* stream);
 
+/* ---- Generation: FP8 (OCP e4m3) KV cache: quantising append and decode attention ----
+ * An FP8 cache is codes [batch, heads_kv, s_max, head_dim], one e4m3 byte each (finite codes only), with unit last
+ *   stride and byte strides {batch, head, position} that are multiples of 8, plus scale [batch, heads_kv, s_max]
+ *   fp32 with element strides {batch, head, position}: one scale per cached head vector, element (.., s, d) has the
+ *   value scale[.., s] * e4m3(codes[.., s, d]). Caches 8-byte, scales 4-byte aligned.
+ * pico_kv_append_fp8: pico_kv_append's contract with that cache. q is rotated in place; k is rotated and written back
+ *   in place in qkv as bf16, and those bf16 values are quantised into k_cache[b, :, p, :] / k_scale[b, :, p]; v is
+ *   quantised into v_cache / v_scale and left untouched in qkv. The quantiser is pico_quantize_rows_fp8's arithmetic
+ *   with a head vector as the row (scale = absmax / 448, a vector of zeros: 1; code = RNE of clamp(x / scale, +-448)).
+ *   A token with p outside [0, min(s_max, table_rows)) is skipped whole: nothing at all is stored. Timed under
+ *   PICO_K_ROPE.
+ * pico_attn_decode_fp8: pico_attn_decode's contract with that cache, o and lse of softmax(softmax_scale q K^T) V on
+ *   the values scale * e4m3(code) in fp32: the score of key s is (q . codes[s]) * k_scale[s] * softmax_scale, the V
+ *   scale multiplies p before the PV accumulation. Codes and scales at or beyond the length are never used (NaN
+ *   codes and NaN scales included). Chunks, workspace (pico_attn_decode_workspace_bytes and
+ *   pico_attn_decode_split_keys for the same shape), determinism and row independence are pico_attn_decode's.
+ *   Timed under PICO_K_ATTN_FWD (chunks) and PICO_K_ATTN_MERGE (combine). */
+int pico_kv_append_fp8(void* qkv, int64_t batch_stride, int64_t token_stride, const void* cos, const void* sin,
+                       int64_t cs_stride, int64_t table_rows, const int32_t* pos, void* k_cache,
+                       const int64_t* k_strides, float* k_scale, const int64_t* k_scale_strides, void* v_cache,
+                       const int64_t* v_strides, float* v_scale, const int64_t* v_scale_strides, int64_t batch,
+                       int64_t tokens, int64_t heads_q, int64_t heads_kv, int64_t s_max, int64_t head_dim,
+                       void* stream);
+int pico_attn_decode_fp8(const void* q, const int64_t* q_strides, const void* k_cache, const int64_t* k_strides,
+                         const float* k_scale, const int64_t* k_scale_strides, const void* v_cache,
+                         const int64_t* v_strides, const float* v_scale, const int64_t* v_scale_strides,
+                         const int32_t* seqlens, void* o, float* lse, void* workspace, int64_t batch, int64_t heads_q,
+                         int64_t heads_kv, int64_t s_max, int64_t head_dim, float softmax_scale, int64_t split_keys,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

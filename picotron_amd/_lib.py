@@ -165,6 +165,14 @@ _SIGNATURES = {
     "pico_decode_linear_fp8_plan": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, c_i64, ctypes.c_int,
                                                    ctypes.POINTER(c_i64)]),
     "pico_decode_linear_fp8": (ctypes.c_int, [ctypes.POINTER(DecodeLinearFp8Args), c_vp]),
+    "pico_kv_append_fp8": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                          c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64),
+                                          c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64),
+                                          c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "pico_attn_decode_fp8": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
+                                            ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
+                                            ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                            c_i64, ctypes.c_float, c_i64, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

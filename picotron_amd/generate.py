@@ -14,6 +14,10 @@ error: there is no eager path on the device.
 
 A decode step performs no host synchronisation: positions and lengths live on the device, shapes are fixed.
 
+An FP8 cache (`KVCache(..., kv_dtype=torch.float8_e4m3fn)`: e4m3 codes plus one fp32 scale per cached head vector)
+takes `pico_kv_append_fp8` (the same rotation; k stays in qkv as bf16 and is quantised into the cache, v is quantised)
+and `pico_attn_decode_fp8` (the same split, half the bytes per key); both ops dispatch on the cache's dtype.
+
 `sample_tokens` is the fused sampler (`pico_sample`: temperature, top-k, top-p, a Philox draw, the EOS / pad rule
 and the output column in one launch, every per-step value in a `SamplerState` on the device); with it a whole
 iteration, decode step and sampler, is captured once as a HIP graph and replayed per token (`generate(graph=True)`).
@@ -29,6 +33,7 @@ import torch.nn as nn
 from . import _lib, ops
 from . import process_group_manager as pgm
 
+_E4M3 = torch.float8_e4m3fn
 MAX_GROUP = 8  # query heads per kv head the decode kernel serves (csrc/attn_decode_plan.h DEC_MAX_GROUP)
 
 
@@ -39,6 +44,26 @@ def _check_caches(k_cache, v_cache, B, D):
     if k_cache.shape != v_cache.shape or k_cache.shape[0] != B or k_cache.shape[3] != D:
         raise ValueError(f"cache shapes {tuple(k_cache.shape)} / {tuple(v_cache.shape)} do not fit batch {B}, "
                          f"head_dim {D}")
+
+
+def _check_scales(who, k_cache, v_cache, k_scale, v_scale, dev):
+    """True for an FP8 cache (e4m3 codes with its two scale tensors [B, Hkv, S_max] fp32); False for a plain one. A
+    cache of one kind with the other's arguments is refused."""
+    fp8 = k_cache.dtype == _E4M3 or v_cache.dtype == _E4M3
+    if not fp8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError(f"{who}: k_scale / v_scale belong to an FP8 (float8_e4m3fn) cache, got {k_cache.dtype}")
+        return False
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"{who}: k_cache is {k_cache.dtype}, v_cache {v_cache.dtype}")
+    if k_scale is None or v_scale is None:
+        raise ValueError(f"{who}: an FP8 cache needs k_scale and v_scale (one fp32 scale per cached head vector)")
+    for t, c, n in ((k_scale, k_cache, "k_scale"), (v_scale, v_cache, "v_scale")):
+        if not isinstance(t, torch.Tensor) or t.shape != c.shape[:3] or t.dtype != torch.float32:
+            raise ValueError(f"{who}: {n} must be fp32 [batch, kv_heads, max_len] = {tuple(c.shape[:3])}")
+        if t.device != c.device or c.device != dev:
+            raise ValueError(f"{who}: {n} on {t.device}, its cache on {c.device}, the input on {dev}")
+    return True
 
 
 def _compute_dtype(t):
@@ -73,13 +98,40 @@ def _kv_append_reference(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv):
         vb[:, p] = xb[tok, Hq + Hkv:].transpose(0, 1).to(v_cache.dtype)
 
 
-def kv_cache_append(qkv, cos, sin, pos, k_cache, v_cache, num_heads, num_kv_heads):
+def _kv_append_fp8_reference(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale, Hq, Hkv):
+    """The reference above into caches of qkv's dtype, the rotated k put back in place in qkv, then the quantiser on
+    the written head vectors."""
+    B, T = qkv.shape[:2]
+    D, S = k_cache.shape[3], k_cache.shape[2]
+    tk = torch.zeros(k_cache.shape, dtype=qkv.dtype)
+    tv = torch.zeros(v_cache.shape, dtype=qkv.dtype)
+    _kv_append_reference(qkv, cos, sin, pos, tk, tv, Hq, Hkv)
+    x = qkv.view(B, T, Hq + 2 * Hkv, D)
+    kb, vb = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
+    for b in range(B):
+        p = int(pos[b]) + torch.arange(T)
+        ok = (p >= 0) & (p < min(S, cos.shape[0]))
+        tok, p = ok.nonzero().flatten(), p[ok]
+        if p.numel() == 0:
+            continue
+        x[b][tok, Hq:Hq + Hkv] = tk[b][:, p].transpose(0, 1)
+        for src, codes, scales in ((tk, kb, k_scale), (tv, vb, v_scale)):
+            c, scales[b][:, p] = ops._quantize_rows_cpu(src[b][:, p].float())  # ops.quantize_weight_fp8's CPU path
+            codes[b][:, p] = c.view(torch.uint8)
+
+
+def kv_cache_append(qkv, cos, sin, pos, k_cache, v_cache, num_heads, num_kv_heads, k_scale=None, v_scale=None):
     """RoPE + KV-cache write for the fused q|k|v projection output `qkv` [B, T, (Hq + 2 Hkv) D].
 
     With p = pos[b] + t (pos: int32 [B] on qkv's device): q[b, t] is rotated IN PLACE with row p of cos / sin
     ([rows, >= D/2] tables), k[b, t] is rotated with row p and stored at k_cache[b, :, p, :], v[b, t] is copied to
     v_cache[b, :, p, :]. Caches are [B, Hkv, S_max, D] views (unit last stride, other strides multiples of 8). A
-    token with p >= S_max, or beyond the tables, is skipped whole. Returns the q view [B, T, Hq, D] of qkv."""
+    token with p >= S_max, or beyond the tables, is skipped whole. Returns the q view [B, T, Hq, D] of qkv.
+
+    FP8 caches (torch.float8_e4m3fn codes, with k_scale / v_scale fp32 [B, Hkv, S_max]: one scale per cached head
+    vector, element = scale * e4m3(code)): the rotated k is ALSO written back in place in qkv (bf16), and those bf16
+    values, and v, are quantised into the caches by ops.quantize_weight_fp8's arithmetic with the head vector as the
+    row. A skipped token stores nothing at all."""
     if qkv.dim() != 3:
         raise ValueError("kv_cache_append: qkv must be [batch, tokens, (heads + 2 kv_heads) * head_dim]")
     B, T, W = qkv.shape
@@ -97,8 +149,21 @@ def kv_cache_append(qkv, cos, sin, pos, k_cache, v_cache, num_heads, num_kv_head
         raise ValueError("kv_cache_append: pos must be int32 [batch] on qkv's device")
     if qkv.stride(2) != 1 or qkv.stride(1) < W:
         raise ValueError("kv_cache_append: qkv rows must be unit-stride (it is rotated in place)")
+    fp8 = _check_scales("kv_cache_append", k_cache, v_cache, k_scale, v_scale, qkv.device)
     if qkv.device.type == "cpu":
-        _kv_append_reference(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv)
+        if fp8:
+            _kv_append_fp8_reference(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale, Hq, Hkv)
+        else:
+            _kv_append_reference(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv)
+    elif fp8:
+        for t, n in ((qkv, "qkv"), (cos, "cos"), (sin, "sin")):
+            ops._need(t, n)
+        _lib.check(_lib.load().pico_kv_append_fp8(
+            _lib.ptr(qkv), qkv.stride(0), qkv.stride(1), _lib.ptr(cos), _lib.ptr(sin), cos.stride(0), cos.shape[0],
+            _lib.ptr(pos), _lib.ptr(k_cache), _lib.i64x3(k_cache.stride()[:3]), _lib.ptr(k_scale),
+            _lib.i64x3(k_scale.stride()), _lib.ptr(v_cache), _lib.i64x3(v_cache.stride()[:3]), _lib.ptr(v_scale),
+            _lib.i64x3(v_scale.stride()), B, T, Hq, Hkv, k_cache.shape[2], D, _lib.stream_of(qkv)),
+            "pico_kv_append_fp8")
     else:
         for t, n in ((qkv, "qkv"), (cos, "cos"), (sin, "sin"), (k_cache, "k_cache"), (v_cache, "v_cache")):
             ops._need(t, n)
@@ -170,14 +235,18 @@ def _workspace(device, nbytes):
     return ws
 
 
-def attention_decode(q, k_cache, v_cache, seqlens, softmax_scale=None, split_keys=None, return_lse=False):
+def attention_decode(q, k_cache, v_cache, seqlens, softmax_scale=None, split_keys=None, return_lse=False,
+                     k_scale=None, v_scale=None):
     """softmax(scale q K^T) V for one query per sequence against a head-major cache.
 
     q [B, Hq, D] (unit last stride; a view of the projection output is fine), k_cache / v_cache [B, Hkv, S_max, D],
     seqlens int32 [B] on q's device: row b attends to keys [0, min(seqlens[b], S_max)). Returns O [B, Hq, D] in q's
     dtype (and LSE [B, Hq] fp32, natural log, with return_lse). seqlens[b] = 0 gives O = 0, LSE = -inf. Hq / Hkv
     may be 1..8. split_keys: keys per chunk of the split (None: the library's host rule, which never reads the
-    device lengths); the result is deterministic for a given split_keys and independent of the other rows."""
+    device lengths); the result is deterministic for a given split_keys and independent of the other rows.
+
+    FP8 caches (float8_e4m3fn codes with k_scale / v_scale fp32 [B, Hkv, S_max]) take pico_attn_decode_fp8: the same
+    attention on the values scale * e4m3(code), in fp32; codes and scales beyond the length are never used."""
     if q.dim() != 3 or q.stride(-1) != 1:
         raise ValueError("attention_decode: q must be [batch, heads, head_dim] with unit last stride")
     B, Hq, D = q.shape
@@ -192,10 +261,15 @@ def attention_decode(q, k_cache, v_cache, seqlens, softmax_scale=None, split_key
     if split_keys is not None and int(split_keys) <= 0:
         raise ValueError("attention_decode: split_keys must be positive")
     scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
+    fp8 = _check_scales("attention_decode", k_cache, v_cache, k_scale, v_scale, q.device)
     if q.device.type == "cpu":
+        if fp8:  # dequantised exactly (fp32 holds scale * e4m3); stale NaNs are dropped by the reference
+            ct = _compute_dtype(q)
+            k_cache = k_cache.float().to(ct) * k_scale.to(ct)[..., None]
+            v_cache = v_cache.float().to(ct) * v_scale.to(ct)[..., None]
         o, lse = _decode_reference(q, k_cache, v_cache, seqlens, scale, split_keys)
         return (o, lse) if return_lse else o
-    for t, n in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache")):
+    for t, n in ((q, "q"),) if fp8 else ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache")):
         ops._need(t, n)
     lib = _lib.load()
     sk = 0 if split_keys is None else int(split_keys)
@@ -206,6 +280,13 @@ def attention_decode(q, k_cache, v_cache, seqlens, softmax_scale=None, split_key
     o = torch.empty((B, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq), dtype=torch.float32, device=q.device)
     qs = (_lib.c_i64 * 2)(q.stride(0), q.stride(1))
+    if fp8:
+        _lib.check(lib.pico_attn_decode_fp8(
+            _lib.ptr(q), qs, _lib.ptr(k_cache), _lib.i64x3(k_cache.stride()[:3]), _lib.ptr(k_scale),
+            _lib.i64x3(k_scale.stride()), _lib.ptr(v_cache), _lib.i64x3(v_cache.stride()[:3]), _lib.ptr(v_scale),
+            _lib.i64x3(v_scale.stride()), _lib.ptr(seqlens), _lib.ptr(o), _lib.ptr(lse), _lib.ptr(ws), B, Hq, Hkv, S,
+            D, scale, sk, _lib.stream_of(q)), "pico_attn_decode_fp8")
+        return (o, lse) if return_lse else o
     _lib.check(lib.pico_attn_decode(_lib.ptr(q), qs, _lib.ptr(k_cache), _lib.i64x3(k_cache.stride()[:3]),
                                     _lib.ptr(v_cache), _lib.i64x3(v_cache.stride()[:3]), _lib.ptr(seqlens),
                                     _lib.ptr(o), _lib.ptr(lse), _lib.ptr(ws), B, Hq, Hkv, S, D, scale, sk,
@@ -241,9 +322,13 @@ def _check_model(model):
 
 class KVCache:
     """Head-major KV cache of a Llama: .k / .v [layers, batch, kv_heads, max_len, head_dim] bf16, .lens int32
-    [batch] on the device (tokens held per row)."""
+    [batch] on the device (tokens held per row).
 
-    def __init__(self, model, batch, max_len, device=None):
+    kv_dtype=torch.float8_e4m3fn: .k / .v hold OCP e4m3 codes and .k_scale / .v_scale [layers, batch, kv_heads,
+    max_len] fp32 one scale per cached head vector (element = scale * e4m3(code)): D + 4 bytes per cached row
+    instead of 2 D. A row is quantised once, when it is appended. None (the default): bf16, no scales."""
+
+    def __init__(self, model, batch, max_len, device=None, kv_dtype=None):
         _check_model(model)
         if max_len > model.max_position_embeddings:
             raise ValueError(f"KVCache: max_len {max_len} exceeds the model's RoPE table "
@@ -252,8 +337,19 @@ class KVCache:
             raise ValueError("KVCache: batch and max_len must be positive")
         device = torch.device(device) if device is not None else model.final_proj.weight.device
         shape = (model.num_layers, batch, model.num_key_values, max_len, model.head_dim)
-        self.k = torch.zeros(shape, dtype=torch.bfloat16, device=device)
-        self.v = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        if kv_dtype not in (None, torch.bfloat16, _E4M3):
+            raise ValueError(f"KVCache: kv_dtype {kv_dtype} is not supported (None / torch.bfloat16, or "
+                             "torch.float8_e4m3fn)")
+        self.kv_dtype = torch.bfloat16 if kv_dtype is None else kv_dtype
+        self.k_scale = self.v_scale = None
+        if self.kv_dtype == _E4M3:  # code 0 with scale 1: a cache of zeros, as the bf16 one
+            self.k = torch.zeros(shape, dtype=torch.uint8, device=device).view(_E4M3)
+            self.v = torch.zeros(shape, dtype=torch.uint8, device=device).view(_E4M3)
+            self.k_scale = torch.ones(shape[:4], dtype=torch.float32, device=device)
+            self.v_scale = torch.ones(shape[:4], dtype=torch.float32, device=device)
+        else:
+            self.k = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+            self.v = torch.zeros(shape, dtype=torch.bfloat16, device=device)
         self.lens = torch.zeros(batch, dtype=torch.int32, device=device)
         self.batch, self.max_len = batch, max_len
         self._plan, self._plan_model = None, None  # prefill's per-layer table (_layer_plan)
@@ -266,7 +362,8 @@ class KVCache:
 def _layer_plan(model, cache, dev):
     """What a pass over the decoder stack reads, gathered once per prefill (a decode step then spends no host time on
     it): per layer the norm weights, the stacked q|k|v and gate|up weights (ops.stacked_weight: the parameters
-    themselves, no copy), the other two projections, the RoPE tables and the layer's cache views."""
+    themselves, no copy), the other two projections, the RoPE tables and the layer's cache views (with the scale
+    views of an FP8 cache, else None)."""
     plan = []
     for i, layer in enumerate(model.decoder_layers):
         a, f = layer.attention, layer.mlp
@@ -276,23 +373,25 @@ def _layer_plan(model, cache, dev):
                      ops.stacked_weight((a.q_proj.weight, a.k_proj.weight, a.v_proj.weight)), a.out_proj.weight,
                      layer.post_attention_layernorm.weight, layer.post_attention_layernorm.eps,
                      ops.stacked_weight((f.gate_proj.weight, f.up_proj.weight)), f.down_proj.weight,
-                     layer.cos, layer.sin, cache.k[i], cache.v[i]))
+                     layer.cos, layer.sin, cache.k[i], cache.v[i],
+                     cache.k_scale[i] if cache.k_scale is not None else None,
+                     cache.v_scale[i] if cache.v_scale is not None else None))
     cache._plan, cache._plan_model = plan, model
     return plan
 
 
 def _layers(model, plan, x, pos, attend):
     """The decoder stack on x [B, T, hidden] with the residual adds fused into the norms, exactly the training
-    forward's rounding points. attend(q, k_cache, v_cache) -> [B, T, Hq * D], after kv_cache_append wrote the
-    cache."""
+    forward's rounding points. attend(q, k_cache, v_cache, k_scale, v_scale) -> [B, T, Hq * D], after kv_cache_append
+    wrote the cache."""
     Hq, Hkv = model.num_heads, model.num_key_values
     B, T = x.shape[:2]
     linear = torch.nn.functional.linear
     delta, residual = x, None
-    for w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc in plan:
+    for w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc, ksc, vsc in plan:
         h, residual = ops.rms_norm(delta, w_in, eps_in, residual=residual, prenorm=True)
-        q = kv_cache_append(linear(h, w_qkv), cos, sin, pos, kc, vc, Hq, Hkv)
-        h2, residual = ops.rms_norm(linear(attend(q, kc, vc), w_out), w_post, eps_post, residual=residual,
+        q = kv_cache_append(linear(h, w_qkv), cos, sin, pos, kc, vc, Hq, Hkv, ksc, vsc)
+        h2, residual = ops.rms_norm(linear(attend(q, kc, vc, ksc, vsc), w_out), w_post, eps_post, residual=residual,
                                     prenorm=True)
         gu = linear(h2, w_gu).view(B * T, -1)
         inter = gu.shape[1] // 2
@@ -392,12 +491,12 @@ def _layers_skinny(model, plan, x, pos, attend, decode_weights=None):
     Hq, Hkv = model.num_heads, model.num_key_values
     B = x.shape[0]
     delta, residual = x.view(B, -1), None
-    for i, (w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc) in enumerate(plan):
+    for i, (w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc, ksc, vsc) in enumerate(plan):
         if decode_weights is not None:
             w_qkv, w_out, w_gu, w_down = decode_weights.layers[i]
         qkv, residual = ops.decode_linear(delta, w_qkv, norm_weight=w_in, eps=eps_in, residual=residual)
-        q = kv_cache_append(qkv.view(B, 1, -1), cos, sin, pos, kc, vc, Hq, Hkv)
-        o = ops.decode_linear(attend(q, kc, vc).view(B, -1), w_out)
+        q = kv_cache_append(qkv.view(B, 1, -1), cos, sin, pos, kc, vc, Hq, Hkv, ksc, vsc)
+        o = ops.decode_linear(attend(q, kc, vc, ksc, vsc).view(B, -1), w_out)
         act, residual = ops.decode_linear(o, w_gu, norm_weight=w_post, eps=eps_post, residual=residual, swiglu=True)
         delta = ops.decode_linear(act, w_down)
     return delta, residual
@@ -407,6 +506,49 @@ def _head_skinny(model, delta, residual, decode_weights=None):
     w = model.final_proj.weight if decode_weights is None else decode_weights.head
     return ops.decode_linear(delta, w, norm_weight=model.final_norm.weight,
                              eps=model.final_norm.eps, residual=residual, out_dtype=torch.float32)[0]
+
+
+@torch.no_grad()
+def reference_logits(model, tokens, num_heads, num_kv_heads, fp8_from=None):
+    """Teacher-forced logits [T, V] of one row of tokens [T], token by token on the CPU restatements of
+    kv_cache_append and attention_decode, in the dtype of the weights (fp32 for a reference): the model-level
+    counterpart of those restatements, for a CPU copy of a Llama (this package's or the oracle's: only the
+    parameters, the norms' eps and the layers' RoPE tables are read). fp8_from=None: an exact cache of that dtype.
+    fp8_from=p: the queries from position p on attend to an FP8 cache (every K / V through the quantiser), the
+    ones before it to the exact cache, as prefill with a prompt of p tokens followed by decode steps does."""
+    lin = torch.nn.functional.linear
+    T, Hq, Hkv = tokens.shape[0], int(num_heads), int(num_kv_heads)
+    w0 = model.embedding.weight
+    D = w0.shape[1] // Hq
+    shape = (len(model.decoder_layers), 1, Hkv, T, D)
+    kx, vx = torch.zeros(shape, dtype=w0.dtype), torch.zeros(shape, dtype=w0.dtype)
+    k8, v8 = torch.zeros(shape, dtype=torch.uint8).view(_E4M3), torch.zeros(shape, dtype=torch.uint8).view(_E4M3)
+    ks, vs = torch.ones(shape[:4]), torch.ones(shape[:4])
+
+    def norm(x, m):
+        return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + m.eps) * m.weight
+
+    out = []
+    for t in range(T):
+        x = w0[tokens[t]].view(1, 1, -1)
+        pos, n = torch.tensor([t], dtype=torch.int32), torch.tensor([t + 1], dtype=torch.int32)
+        for i, layer in enumerate(model.decoder_layers):
+            a, f, h = layer.attention, layer.mlp, norm(x, layer.input_layernorm)
+            qkv = torch.cat([lin(h, a.q_proj.weight), lin(h, a.k_proj.weight), lin(h, a.v_proj.weight)], -1)
+            cos, sin = layer.cos[:, : D // 2].to(w0.dtype), layer.sin[:, : D // 2].to(w0.dtype)
+            if fp8_from is not None:
+                kv_cache_append(qkv.clone(), cos, sin, pos, k8[i], v8[i], Hq, Hkv, k_scale=ks[i], v_scale=vs[i])
+            q = kv_cache_append(qkv, cos, sin, pos, kx[i], vx[i], Hq, Hkv)[:, 0]
+            if fp8_from is not None and t >= fp8_from:
+                o = attention_decode(q, k8[i], v8[i], n, k_scale=ks[i], v_scale=vs[i])
+            else:
+                o = attention_decode(q, kx[i], vx[i], n)
+            x = x + lin(o.view(1, 1, -1), a.out_proj.weight)
+            h = norm(x, layer.post_attention_layernorm)
+            x = x + lin(torch.nn.functional.silu(lin(h, f.gate_proj.weight)) * lin(h, f.up_proj.weight),
+                        f.down_proj.weight)
+        out.append(lin(norm(x, model.final_norm), model.final_proj.weight)[0, 0])
+    return torch.stack(out)
 
 
 def _check_cache(model, cache, B):
@@ -419,7 +561,11 @@ def prefill(model, input_ids, cache, prompt_lens=None):
     """Run the prompts through the model and fill `cache` from position 0: returns the fp32 logits [B, V] of each
     row's last prompt token. input_ids [B, T] is right-padded to a common length; prompt_lens (int tensor or list,
     default T for every row) gives the rows' true lengths. The padding positions are written to the cache too, but
-    lie at or beyond the row's length: decode steps overwrite them before they can be read."""
+    lie at or beyond the row's length: decode steps overwrite them before they can be read.
+
+    With an FP8 cache the prompt attention reads the bf16 K / V where kv_cache_append left them, in the projection
+    output (strided views, through the attention kernel's stride arguments): the prompt is attended exactly as
+    with a bf16 cache, and the cache receives the quantised copy."""
     _check_model(model)
     if input_ids.dim() != 2:
         raise ValueError("prefill: input_ids must be [batch, tokens]")
@@ -436,12 +582,18 @@ def prefill(model, input_ids, cache, prompt_lens=None):
             raise ValueError("prefill: prompt_lens must have one entry per row")
         if isinstance(prompt_lens, (list, tuple)) and not all(1 <= int(n) <= T for n in prompt_lens):
             raise ValueError(f"prefill: prompt_lens must lie in [1, {T}]")
-    Hq, D = model.num_heads, model.head_dim
+    Hq, Hkv, D = model.num_heads, model.num_key_values, model.head_dim
     pos = torch.zeros(B, dtype=torch.int32, device=dev)
     scale = 1.0 / math.sqrt(D)
 
-    def attend(q, kc, vc):
-        o, _ = ops.attention_block_fwd(q, kc.transpose(1, 2)[:, :T], vc.transpose(1, 2)[:, :T], scale, True)
+    def attend(q, kc, vc, ksc, vsc):
+        if ksc is None:
+            k, v = kc.transpose(1, 2)[:, :T], vc.transpose(1, 2)[:, :T]
+        else:  # the rotated k and the v of the projection output q is a view of
+            st, off = (q.stride(0), q.stride(1), D, 1), q.storage_offset()
+            k = q.as_strided((B, T, Hkv, D), st, off + Hq * D)
+            v = q.as_strided((B, T, Hkv, D), st, off + (Hq + Hkv) * D)
+        o, _ = ops.attention_block_fwd(q, k, v, scale, True)
         return o.view(B, T, Hq * D)
 
     x = torch.nn.functional.embedding(input_ids, model.embedding.weight)
@@ -457,7 +609,8 @@ def prefill(model, input_ids, cache, prompt_lens=None):
 def decode_step(model, tokens, cache, skinny_linear=False, decode_weights=None):
     """One token per row: tokens int64 [B] -> fp32 logits [B, V] of the next token; the cache grows by one. No host
     synchronisation: the positions are cache.lens on the device. A row whose cache is full writes nothing and
-    attends to the full cache (generate() refuses lengths that would get there).
+    attends to the full cache (generate() refuses lengths that would get there). The cache's own format decides
+    the kernels: an FP8 KVCache appends through pico_kv_append_fp8 and attends through pico_attn_decode_fp8.
 
     skinny_linear=True (B <= 16): the projections run on ops.decode_linear, one pass over each weight with the norm
     before it and the SwiGLU after it in the same launch, instead of F.linear and the row-wise kernels beside it.
@@ -483,8 +636,8 @@ def decode_step(model, tokens, cache, skinny_linear=False, decode_weights=None):
     Hq, D = model.num_heads, model.head_dim
     seqlens = cache.lens + 1
 
-    def attend(q, kc, vc):
-        return attention_decode(q.view(B, Hq, D), kc, vc, seqlens).view(B, 1, Hq * D)
+    def attend(q, kc, vc, ksc, vsc):
+        return attention_decode(q.view(B, Hq, D), kc, vc, seqlens, k_scale=ksc, v_scale=vsc).view(B, 1, Hq * D)
 
     x = torch.nn.functional.embedding(tokens.view(B, 1), model.embedding.weight)
     if skinny_linear:
@@ -719,7 +872,7 @@ def _capture_stream(device):
     return torch.cuda.graph.default_capture_stream
 
 
-def _generate_cache(model, input_ids, max_new_tokens, cache):
+def _generate_cache(model, input_ids, max_new_tokens, cache, kv_dtype=None):
     """generate()'s checks of its arguments, and the cache it runs on: the caller's, reset, or a new one of exactly
     the needed length."""
     _check_model(model)
@@ -733,8 +886,10 @@ def _generate_cache(model, input_ids, max_new_tokens, cache):
         if need > model.max_position_embeddings:
             raise ValueError(f"generate: prompt {T} + {max_new_tokens} new tokens exceed the model's "
                              f"max_position_embeddings {model.max_position_embeddings}")
-        return KVCache(model, B, need, device=input_ids.device)
+        return KVCache(model, B, need, device=input_ids.device, kv_dtype=kv_dtype)
     _check_cache(model, cache, B)
+    if kv_dtype is not None and cache.kv_dtype != kv_dtype:
+        raise ValueError(f"generate: kv_dtype {kv_dtype} does not match the given cache's {cache.kv_dtype}")
     if need > cache.max_len:
         raise ValueError(f"generate: prompt {T} + {max_new_tokens} new tokens exceed the cache's max_len "
                          f"{cache.max_len}")
@@ -743,8 +898,9 @@ def _generate_cache(model, input_ids, max_new_tokens, cache):
 
 
 def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p, eos_token_id,
-                    pad_token_id, seed, return_logits, cache, graph, skinny_linear=False, decode_weights=None):
-    cache = _generate_cache(model, input_ids, max_new_tokens, cache)
+                    pad_token_id, seed, return_logits, cache, graph, skinny_linear=False, decode_weights=None,
+                    kv_dtype=None):
+    cache = _generate_cache(model, input_ids, max_new_tokens, cache, kv_dtype)
     B, N = input_ids.shape[0], max_new_tokens
     dev = input_ids.device
     settings = dict(temperature=temperature, top_k=top_k, top_p=top_p, eos_token_id=eos_token_id,
@@ -809,7 +965,7 @@ def _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, 
 @torch.no_grad()
 def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0, top_k=None, eos_token_id=None,
              pad_token_id=0, generator=None, return_logits=False, cache=None, top_p=None, seed=None, graph=False,
-             skinny_linear=False, decode_weights=None):
+             skinny_linear=False, decode_weights=None, kv_dtype=None):
     """Sample max_new_tokens tokens per row after the (right-padded) prompts: int64 [B, max_new_tokens], and with
     return_logits the fp32 [B, max_new_tokens, V] each token was drawn from. One prefill, then max_new_tokens - 1
     decode steps. A row that has emitted eos_token_id yields pad_token_id from then on (masked on the device; no
@@ -828,7 +984,10 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
     decode_weights (quantize_decode_weights(model), with skinny_linear=True only): the decode steps' projections
     stream FP8 (e4m3) weights, half the bytes of the bf16 ones. Prefill keeps running on the bf16 weights and the
     training kernels: the prompt's K/V come from the bf16 weights, the generated tokens' from the FP8 ones. The
-    object is a snapshot of the model's weights; a captured graph is keyed by its identity as well."""
+    object is a snapshot of the model's weights; a captured graph is keyed by its identity as well.
+
+    kv_dtype=torch.float8_e4m3fn: the cache generate() allocates is an FP8 KVCache (about half the K / V bytes per
+    decode step); with cache= given it must match that cache's. The prompt is attended on the bf16 K / V."""
     if decode_weights is not None:
         _check_decode_weights(model, decode_weights, skinny_linear)
     if skinny_linear:
@@ -839,8 +998,8 @@ def generate(model, input_ids, max_new_tokens, prompt_lens=None, temperature=0.0
                              "draws from its seed)")
         return _generate_fused(model, input_ids, max_new_tokens, prompt_lens, temperature, top_k, top_p,
                                eos_token_id, pad_token_id, seed, return_logits, cache, graph, skinny_linear,
-                               decode_weights)
-    cache = _generate_cache(model, input_ids, max_new_tokens, cache)
+                               decode_weights, kv_dtype)
+    cache = _generate_cache(model, input_ids, max_new_tokens, cache, kv_dtype)
     B = input_ids.shape[0]
     dev = input_ids.device
     out = torch.empty((B, max_new_tokens), dtype=torch.int64, device=dev)

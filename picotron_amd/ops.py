@@ -1554,6 +1554,13 @@ class Fp8Weight:
         return (self.codes.float() * self.scale[:, None]).to(dtype)
 
 
+def _quantize_rows_cpu(wf):
+    """quantize_weight_fp8's arithmetic on fp32 rows [..., K] in plain torch: (codes e4m3, scale fp32 [...])."""
+    a = wf.abs().amax(-1)
+    scale = torch.where(a == 0, torch.ones_like(a), a / E4M3_MAX)
+    return (wf / scale[..., None]).clamp(-E4M3_MAX, E4M3_MAX).to(_E4M3), scale
+
+
 def quantize_weight_fp8(weight):
     """Fp8Weight of a bf16 weight [N, K] (or of the tuple ops.stacked_weight takes: the stacked view is quantised,
     no bf16 copy), one scale per row: scale = absmax / 448 (fp32 division; a row of zeros: 1), code = RNE to e4m3 of
@@ -1564,9 +1571,7 @@ def quantize_weight_fp8(weight):
         raise ValueError("quantize_weight_fp8: weight must be a bf16 [N, K] matrix with unit last stride")
     N, K = w.shape
     if w.device.type == "cpu":
-        a = w.float().abs().amax(1)
-        scale = torch.where(a == 0, torch.ones_like(a), a / E4M3_MAX)
-        return Fp8Weight((w.float() / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(_E4M3), scale)
+        return Fp8Weight(*_quantize_rows_cpu(w.float()))
     _need(w, "weight")
     if K % 8 or w.stride(0) % 8:
         raise ValueError(f"quantize_weight_fp8: K = {K} and the row stride must be multiples of 8")

@@ -10,13 +10,18 @@ repository.
            of the live context, q, O) over the time, as GB/s and as a share of the 8 TB/s HBM peak, the default
            split, and, from a pass of its own with the library's per-launch events (pico_prof_*), the time of the
            two kernels alone with the same two rates.
+  kv_fp8   the same shapes and method for pico_attn_decode_fp8 beside pico_attn_decode, alternated in one process:
+           the FP8 cache holds the quantised bf16 cache (ops.quantize_weight_fp8 per head vector). One JSON line per
+           shape: us per call of both, each one's two kernels alone (per-launch events, a pass each), and each one's
+           algorithmic bytes (FP8: D + 4 bytes per cached row for K and for V) over the kernel time as a share of
+           the HBM peak.
   e2e      SmolLM-1.7B geometry, --layers layers (15), B in {1, 8}, a 128-token prompt, 128 new tokens, greedy:
            generate() against what the training forward alone offers, model(prefix) recomputed for every token
            (host clock around the whole loop, ending in a synchronise, after one warm pass of each). Reports ms per
            generated token for both, prefill and decode step separately, and the floor of streaming the weights
            (decoder matrices + LM head, bf16) once per step at 8 TB/s.
 
-Usage: python scripts/decode_bench.py kernels|e2e [--out profiles/decode_bench.jsonl] [--iters 200] [--rounds 3]
+Usage: python scripts/decode_bench.py kernels|kv_fp8|e2e [--out profiles/decode_bench.jsonl] [--iters 200] [--rounds 3]
 """
 import argparse
 import json
@@ -133,6 +138,59 @@ def kernels(args):
                 del k, v
 
 
+def kv_fp8(args):
+    from picotron_amd import _lib as L
+    from picotron_amd import generate as G
+    from picotron_amd import ops
+    dev = torch.device("cuda", 0)
+    for Hq, Hkv, D in ((32, 32, 64), (32, 8, 128)):
+        for B in (1, 8, 32):
+            for ctx in (1024, 8192):
+                rows = B * Hkv * ctx
+                nbuf = max(1, min(64, math.ceil(args.rotate_mb * (1 << 20) / (2 * rows * D * 2))))
+                kv = [torch.empty(nbuf, B, Hkv, ctx, D, device=dev, dtype=torch.bfloat16).normal_() for _ in range(2)]
+                kv8 = [ops.quantize_weight_fp8(t.view(-1, D)) for t in kv]
+                codes = [w.codes.view(nbuf, B, Hkv, ctx, D) for w in kv8]
+                scales = [w.scale.view(nbuf, B, Hkv, ctx) for w in kv8]
+                q = torch.randn(B, Hq, D, device=dev).to(torch.bfloat16)
+                lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+
+                def bf16(i):
+                    return G.attention_decode(q, kv[0][i % nbuf], kv[1][i % nbuf], lens)
+
+                def fp8(i):
+                    return G.attention_decode(q, codes[0][i % nbuf], codes[1][i % nbuf], lens,
+                                              k_scale=scales[0][i % nbuf], v_scale=scales[1][i % nbuf])
+
+                forms = {"bf16": bf16, "fp8": fp8}
+                diff = float((bf16(0).float() - fp8(0).float()).abs().max())  # the quantisation's effect on O
+                for fn in forms.values():
+                    for i in range(max(nbuf, 8)):
+                        fn(i)
+                us = {name: [] for name in forms}
+                for _ in range(args.rounds):
+                    for name, fn in forms.items():
+                        us[name].append(_events_us(fn, args.iters))
+                algo = {"bf16": 2 * rows * D * 2 + 2 * B * Hq * D * 2, "fp8": 2 * rows * (D + 4) + 2 * B * Hq * D * 2}
+                rec = {"mode": "kv_fp8", "Hq": Hq, "Hkv": Hkv, "D": D, "B": B, "context": ctx,
+                       "split_keys": G.default_split_keys(B, Hkv, ctx, D), "cache_copies": nbuf,
+                       "max_abs_diff_fp8_vs_bf16": diff}
+                for name, fn in forms.items():  # the two kernels alone, a pass of per-launch events for each form
+                    for kid in (L.K_ATTN_FWD, L.K_ATTN_MERGE):
+                        L.prof_enable(kid, args.iters)
+                    for i in range(args.iters):
+                        fn(i)
+                    kus = sum(1e3 * L.prof_collect(kid)[0] / args.iters for kid in (L.K_ATTN_FWD, L.K_ATTN_MERGE))
+                    L.load().pico_prof_enable(0, 0)
+                    med = sorted(us[name])[len(us[name]) // 2]
+                    rec.update({f"{name}_us_rounds": [round(x, 2) for x in us[name]], f"{name}_us": round(med, 2),
+                                f"{name}_kernels_us": round(kus, 2), f"{name}_algorithmic_bytes": algo[name],
+                                f"{name}_kernels_frac_of_8TBs": round(algo[name] / (kus * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)})
+                rec["fp8_over_bf16_kernels"] = round(rec["fp8_kernels_us"] / rec["bf16_kernels_us"], 3)
+                _emit(args, rec)
+                del kv, kv8, codes, scales
+
+
 def _clock_ms(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -207,7 +265,7 @@ def e2e(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["kernels", "e2e"])
+    ap.add_argument("mode", choices=["kernels", "kv_fp8", "e2e"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_bench.jsonl"),
                     help="append the JSON lines to this file")
     ap.add_argument("--iters", type=int, default=200)
@@ -217,4 +275,4 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("decode_bench: needs a HIP device (no measurement without one)")
-    kernels(a) if a.mode == "kernels" else e2e(a)
+    {"kernels": kernels, "kv_fp8": kv_fp8, "e2e": e2e}[a.mode](a)

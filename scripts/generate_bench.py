@@ -14,7 +14,11 @@ device; reads nothing outside the repository.
            --rounds rounds, medians. The decode step over the weight-streaming floor as scripts/decode_bench.py
            defines it (prefill taken from the same rounds).
 
-Usage: python scripts/generate_bench.py sampler|e2e [--out profiles/generate_bench.jsonl] [--iters 200] [--rounds 3]
+  e2e_long the long-context row: a 2048-token prompt and 128 new tokens at B in {1, 8} on the best route (graph=True,
+           skinny_linear=True, FP8 decode weights), with the bf16 KV cache and with the FP8 KV cache
+           (kv_dtype=torch.float8_e4m3fn), alternated; the decode step is (whole call - prefill) / 127.
+
+Usage: python scripts/generate_bench.py sampler|e2e|e2e_long [--out profiles/generate_bench.jsonl] [--iters 200] [--rounds 3]
 """
 import argparse
 import json
@@ -200,9 +204,56 @@ def e2e(args):
         _emit(args, rec)
 
 
+def e2e_long(args):
+    from picotron_amd import generate as G
+    from picotron_amd.model import build_llama, smollm_1_7b
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    P, N = 2048, 128
+    cfg = smollm_1_7b(num_hidden_layers=args.layers, seq_length=4096)
+    torch.manual_seed(0)
+    model = build_llama(cfg, device=dev)
+    with torch.no_grad():
+        model.final_proj.weight.normal_(0.0, 0.02)
+    w8 = G.quantize_decode_weights(model)
+    L, Hkv, D = cfg.num_hidden_layers, cfg.num_key_value_heads, model.head_dim
+    for B in (1, 8):
+        prompt = torch.randint(0, cfg.vocab_size, (B, P), generator=torch.Generator().manual_seed(B)).to(dev)
+        caches = {"bf16_cache": G.KVCache(model, B, P + N),
+                  "fp8_cache": G.KVCache(model, B, P + N, kv_dtype=torch.float8_e4m3fn)}
+        out, forms = {}, {}
+        for name, c in caches.items():
+            def whole(name=name, c=c):
+                out[name] = G.generate(model, prompt, N, cache=c, graph=True, skinny_linear=True, decode_weights=w8)
+
+            def prefill_only(c=c):
+                c.reset()
+                G.prefill(model, prompt, c)
+
+            forms[name], forms[name + "_prefill"] = whole, prefill_only
+        for name, fn in forms.items():
+            _clock_ms(fn)
+            _log(f"B={B} warm {name} done")
+        ms = {name: [] for name in forms}
+        for _ in range(args.rounds):
+            for name, fn in forms.items():
+                ms[name].append(_clock_ms(fn))
+        med = {name: _median(x) for name, x in ms.items()}
+        rec = {"mode": "e2e_long", "model": f"SmolLM-1.7B geometry, {args.layers} layers", "B": B, "prompt": P,
+               "new_tokens": N, "route": "graph + skinny_linear + FP8 decode weights"}
+        for name, per_row in (("bf16_cache", 2 * D), ("fp8_cache", D + 4)):
+            rec[name + "_ms_rounds"] = [round(x, 1) for x in ms[name]]
+            rec[name + "_prefill_ms"] = round(med[name + "_prefill"], 2)
+            rec[name + "_decode_step_ms"] = round((med[name] - med[name + "_prefill"]) / (N - 1), 4)
+            rec[name + "_kv_bytes_per_step_at_end"] = 2 * L * B * Hkv * (P + N) * per_row
+        rec["fp8_over_bf16_decode_step"] = round(rec["fp8_cache_decode_step_ms"] / rec["bf16_cache_decode_step_ms"], 3)
+        rec["tokens_equal_fraction"] = round(float((out["bf16_cache"] == out["fp8_cache"]).float().mean()), 4)
+        _emit(args, rec)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["sampler", "e2e"])
+    ap.add_argument("mode", choices=["sampler", "e2e", "e2e_long"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generate_bench.jsonl"),
                     help="append the JSON lines to this file")
     ap.add_argument("--iters", type=int, default=200)
@@ -211,4 +262,4 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("generate_bench: needs a HIP device (no measurement without one)")
-    sampler(a) if a.mode == "sampler" else e2e(a)
+    {"sampler": sampler, "e2e": e2e, "e2e_long": e2e_long}[a.mode](a)
