@@ -489,6 +489,30 @@ int pico_attn_decode(const void* q, const int64_t* q_strides, const void* k_cach
                      void* workspace, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t s_max,
                      int64_t head_dim, float softmax_scale, int64_t split_keys, void* stream);
 
+/* ---- Generation: multi-token extend attention (no reference call) ----
+ * pico_attn_extend: tokens (1..16; more is refused) new queries per sequence against the same bf16 caches, on the
+ *   matrix unit. q[b, t, h] at q + b * q_strides[0] + t * q_strides[1] + h * q_strides[2] (head_dim bf16, already
+ *   rotated: the q view pico_kv_append leaves), seqlens DEVICE int32 [batch] = the keys the LAST query of the row
+ *   sees (the row's length after the append) -> o [batch, tokens, heads_q, head_dim] bf16 and lse [batch, tokens,
+ *   heads_q] fp32 (natural log), both contiguous. Query t attends to keys [0, clamp(seqlens[b] - (tokens - 1 - t),
+ *   0, s_max)); a query with no visible key gives o = 0, lse = -inf. Cache rows at or beyond clamp(seqlens[b]) are
+ *   never used; the rows between a query's own limit and that length (the later new tokens) must be finite.
+ *   heads_q / heads_kv at most 8. A workgroup serves up to 32 of the tokens * heads_q / heads_kv query rows of a kv
+ *   head over a chunk of split_keys keys and writes an fp32 partial to the workspace; a second kernel combines a
+ *   row's chunks in chunk order. No atomics, no inter-workgroup waiting: the same inputs and split_keys give the
+ *   same bits, and a batch row's result does not depend on the other rows. split_keys <= 0 selects
+ *   pico_attn_extend_split_keys (a host rule on the shape and the CU count, never on the device lengths; -1 for bad
+ *   arguments). workspace: pico_attn_extend_workspace_bytes for the same arguments (-1 for bad arguments). Timed
+ *   under PICO_K_ATTN_FWD (chunks) and PICO_K_ATTN_MERGE (combine). */
+int64_t pico_attn_extend_split_keys(int64_t batch, int64_t tokens, int64_t heads_q, int64_t heads_kv, int64_t s_max,
+                                    int64_t head_dim);
+int64_t pico_attn_extend_workspace_bytes(int64_t batch, int64_t tokens, int64_t heads_q, int64_t heads_kv,
+                                         int64_t s_max, int64_t head_dim, int64_t split_keys);
+int pico_attn_extend(const void* q, const int64_t* q_strides, const void* k_cache, const int64_t* k_strides,
+                     const void* v_cache, const int64_t* v_strides, const int32_t* seqlens, void* o, float* lse,
+                     void* workspace, int64_t batch, int64_t tokens, int64_t heads_q, int64_t heads_kv, int64_t s_max,
+                     int64_t head_dim, float softmax_scale, int64_t split_keys, void* stream);
+
 /* ---- Generation: fused device sampler (no reference call: the reference has no sampling path) ----
  * pico_sample: one launch per decode step, one workgroup per row of logits [rows, vocab] (dtype PICO_SAMPLE_F32 or
  *   PICO_SAMPLE_BF16, row r at logits + r * row_stride elements, unit last stride, 1 <= vocab <= 2^20, no

@@ -154,6 +154,11 @@ _SIGNATURES = {
     "pico_attn_decode": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
                                         ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
                                         c_i64, ctypes.c_float, c_i64, c_vp]),
+    "pico_attn_extend_split_keys": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "pico_attn_extend_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "pico_attn_extend": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
+                                        ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                        c_i64, c_i64, ctypes.c_float, c_i64, c_vp]),
     "pico_sample": (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                    c_vp, c_vp]),
     "pico_decode_linear_args_size": (c_i64, []),

@@ -18,6 +18,11 @@ An FP8 cache (`KVCache(..., kv_dtype=torch.float8_e4m3fn)`: e4m3 codes plus one 
 takes `pico_kv_append_fp8` (the same rotation; k stays in qkv as bf16 and is quantised into the cache, v is quantised)
 and `pico_attn_decode_fp8` (the same split, half the bytes per key); both ops dispatch on the cache's dtype.
 
+`extend_step` runs T <= 16 tokens per row in one pass over the weights (verifying drafted tokens, continuing a cached
+conversation, scoring against a long cache): `kv_cache_append` with T tokens, then `attention_extend`
+(`pico_attn_extend`: the T x Hq / Hkv query rows of a kv head on the matrix unit, split over the keys like the decode
+kernel, bf16 caches only). `KVCache.rewind` takes rejected tokens back on the device.
+
 `sample_tokens` is the fused sampler (`pico_sample`: temperature, top-k, top-p, a Philox draw, the EOS / pad rule
 and the output column in one launch, every per-step value in a `SamplerState` on the device); with it a whole
 iteration, decode step and sampler, is captured once as a HIP graph and replayed per token (`generate(graph=True)`).
@@ -35,6 +40,7 @@ from . import process_group_manager as pgm
 
 _E4M3 = torch.float8_e4m3fn
 MAX_GROUP = 8  # query heads per kv head the decode kernel serves (csrc/attn_decode_plan.h DEC_MAX_GROUP)
+MAX_EXTEND_TOKENS = 16  # new tokens per row the extend kernel serves (csrc/attn_extend_plan.h EXT_MAX_TOKENS)
 
 
 def _check_caches(k_cache, v_cache, B, D):
@@ -295,6 +301,109 @@ def attention_decode(q, k_cache, v_cache, seqlens, softmax_scale=None, split_key
 
 
 # --------------------------------------------------------------------------------------------
+# Extend attention: T <= 16 new queries per sequence
+# --------------------------------------------------------------------------------------------
+def default_extend_split_keys(batch, tokens, num_heads, num_kv_heads, max_len, head_dim):
+    """The library's host rule for pico_attn_extend's chunk length (shape and CU count only;
+    csrc/attn_extend_plan.h)."""
+    return int(_lib.load().pico_attn_extend_split_keys(batch, tokens, num_heads, num_kv_heads, max_len, head_dim))
+
+
+def _extend_reference(q, k_cache, v_cache, seqlens, scale, split_keys):
+    """attention_extend's contract in plain torch: per chunk (m, l, o) against the chunk's own maximum, combined in
+    chunk order. bf16 inputs: fp32 scores, p rounded to bf16 before the PV product (l sums the unrounded p), as the
+    kernel; other dtypes: their compute dtype throughout."""
+    B, T, Hq, D = q.shape
+    Hkv, S = k_cache.shape[1], k_cache.shape[2]
+    G = Hq // Hkv
+    ct = _compute_dtype(q)
+    sk = S if split_keys is None else int(split_keys)
+    nsplit = (S + sk - 1) // sk
+    pad = nsplit * sk - S
+    raw = seqlens.to(torch.int64)
+    keys = torch.arange(S)
+    live = keys[None, :] < raw.clamp(0, S)[:, None]                                    # [B, S]
+    vis = keys[None, None, :] < (raw[:, None] - (T - 1 - torch.arange(T))[None, :]).clamp(0, S)[:, :, None]  # [B, T, S]
+    sel = live[:, None, :, None]
+    # contents at or beyond the length never reach the result (a stale NaN times p = 0 would)
+    kf = torch.where(sel, k_cache.to(ct), torch.zeros((), dtype=ct))
+    vf = torch.where(sel, v_cache.to(ct), torch.zeros((), dtype=ct))
+    s = torch.einsum("bthgd,bhsd->bhtgs", q.to(ct).reshape(B, T, Hkv, G, D), kf) * scale
+    s = s.masked_fill(~vis[:, None, :, None, :], float("-inf"))
+    if pad:
+        s = torch.nn.functional.pad(s, (0, pad), value=float("-inf"))
+        vf = torch.nn.functional.pad(vf, (0, 0, 0, pad))
+    s = s.view(B, Hkv, T, G, nsplit, sk)
+    vf = vf.view(B, Hkv, nsplit, sk, D)
+    m = s.amax(dim=-1)
+    ms = torch.where(torch.isinf(m) & (m < 0), torch.zeros_like(m), m)
+    p = torch.exp(s - ms[..., None])
+    l = p.sum(dim=-1)
+    if q.dtype == torch.bfloat16:
+        p = p.to(torch.bfloat16).to(ct)
+    o = torch.einsum("bhtgcs,bhcsd->bhtgcd", p, vf)
+    mt = m.amax(dim=-1)
+    mts = torch.where(torch.isinf(mt) & (mt < 0), torch.zeros_like(mt), mt)
+    w = torch.exp(m - mts[..., None])
+    lt = (l * w).sum(dim=-1)
+    ot = (o * w[..., None]).sum(dim=-2)
+    any_ = lt > 0
+    out = torch.where(any_[..., None], ot / lt.clamp_min(torch.finfo(ct).tiny)[..., None], torch.zeros((), dtype=ct))
+    lse = torch.where(any_, mt + torch.log(lt), torch.full((), float("-inf"), dtype=ct))
+    return out.permute(0, 2, 1, 3, 4).reshape(B, T, Hq, D).to(q.dtype), lse.permute(0, 2, 1, 3).reshape(B, T, Hq)
+
+
+def attention_extend(q, k_cache, v_cache, seqlens, softmax_scale=None, split_keys=None, return_lse=False):
+    """softmax(scale q K^T) V for T <= 16 new queries per sequence against a head-major bf16 cache that already
+    holds their keys (pico_attn_extend: split over the keys, on the matrix unit).
+
+    q [B, T, Hq, D] (unit last stride; the view kv_cache_append returns), k_cache / v_cache [B, Hkv, S_max, D],
+    seqlens int32 [B] on q's device: the keys the LAST query of the row sees, i.e. the row's length after the
+    append. Query t attends to keys [0, clamp(seqlens[b] - (T - 1 - t), 0, S_max)). Returns O [B, T, Hq, D] in q's
+    dtype (and LSE [B, T, Hq] fp32, natural log, with return_lse); a query with no visible key gives O = 0,
+    LSE = -inf. Hq / Hkv may be 1..8. split_keys: keys per chunk (None: the library's host rule, which never reads
+    the device lengths); deterministic for a given split_keys, a row independent of the other rows. CPU tensors run
+    the plain-torch restatement (fp64 inputs: fp64 throughout, the reference). An FP8 cache is refused."""
+    if q.dim() != 4 or q.stride(-1) != 1:
+        raise ValueError("attention_extend: q must be [batch, tokens, heads, head_dim] with unit last stride")
+    B, T, Hq, D = q.shape
+    if not 1 <= T <= MAX_EXTEND_TOKENS:
+        raise ValueError(f"attention_extend: {T} tokens per row; 1 to {MAX_EXTEND_TOKENS} are supported")
+    if k_cache.dtype == _E4M3 or v_cache.dtype == _E4M3:
+        raise ValueError("attention_extend: this kernel reads bf16 caches only, not an FP8 (float8_e4m3fn) cache")
+    _check_caches(k_cache, v_cache, B, D)
+    Hkv, S = k_cache.shape[1], k_cache.shape[2]
+    if Hq % Hkv:
+        raise ValueError(f"attention_extend: {Hq} query heads are not a multiple of {Hkv} kv heads")
+    if Hq // Hkv > MAX_GROUP:
+        raise ValueError(f"attention_extend: {Hq // Hkv} query heads per kv head; at most {MAX_GROUP} are supported")
+    if seqlens.shape != (B,) or seqlens.dtype != torch.int32 or seqlens.device != q.device:
+        raise ValueError("attention_extend: seqlens must be int32 [batch] on q's device")
+    if split_keys is not None and int(split_keys) <= 0:
+        raise ValueError("attention_extend: split_keys must be positive")
+    scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
+    if q.device.type == "cpu":
+        o, lse = _extend_reference(q, k_cache, v_cache, seqlens, scale, split_keys)
+        return (o, lse) if return_lse else o
+    for t, n in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache")):
+        ops._need(t, n)
+    lib = _lib.load()
+    sk = 0 if split_keys is None else int(split_keys)
+    nbytes = int(lib.pico_attn_extend_workspace_bytes(B, T, Hq, Hkv, S, D, sk))
+    if nbytes < 0:
+        raise RuntimeError("attention_extend: " + lib.pico_last_error().decode(errors="replace"))
+    ws = _workspace(q.device, nbytes)
+    o = torch.empty((B, T, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, T, Hq), dtype=torch.float32, device=q.device)
+    _lib.check(lib.pico_attn_extend(_lib.ptr(q), _lib.i64x3(q.stride()[:3]), _lib.ptr(k_cache),
+                                    _lib.i64x3(k_cache.stride()[:3]), _lib.ptr(v_cache),
+                                    _lib.i64x3(v_cache.stride()[:3]), _lib.ptr(seqlens), _lib.ptr(o), _lib.ptr(lse),
+                                    _lib.ptr(ws), B, T, Hq, Hkv, S, D, scale, sk, _lib.stream_of(q)),
+               "pico_attn_extend")
+    return (o, lse) if return_lse else o
+
+
+# --------------------------------------------------------------------------------------------
 # Model level
 # --------------------------------------------------------------------------------------------
 def _check_model(model):
@@ -357,6 +466,18 @@ class KVCache:
 
     def reset(self):
         self.lens.zero_()
+
+    def rewind(self, n):
+        """Drop the last n tokens of every row (n: int >= 0), or n[b] of row b (int32 [batch] on the cache's device):
+        lens = max(lens - n, 0), on the device, no synchronisation. The dropped rows stay in the cache beyond the
+        length, where nothing reads them, until the next append overwrites them. With extend_step this is what a
+        speculative or lookup loop needs to take back rejected drafts."""
+        if isinstance(n, torch.Tensor):
+            if n.shape != (self.batch,) or n.dtype != torch.int32 or n.device != self.lens.device:
+                raise ValueError("KVCache.rewind: a tensor n must be int32 [batch] on the cache's device")
+        elif not isinstance(n, int) or isinstance(n, bool) or n < 0:
+            raise ValueError("KVCache.rewind: n must be a non-negative int or an int32 [batch] tensor")
+        self.lens.sub_(n).clamp_(min=0)
 
 
 def _layer_plan(model, cache, dev):
@@ -484,19 +605,20 @@ def _check_decode_weights(model, w, skinny_linear):
 
 
 def _layers_skinny(model, plan, x, pos, attend, decode_weights=None):
-    """_layers for a decode step (x [B <= 16, 1, hidden]) on ops.decode_linear: each norm runs inside the projection
-    after it and the SwiGLU inside gate|up, with _layers' rounding points. Per layer: norm + q|k|v, the cache
-    append, the decode attention, the out projection, norm + gate|up + SwiGLU, the down projection. decode_weights:
-    the four projections read its Fp8Weights instead of the plan's bf16 weights."""
+    """_layers for a decode step (x [B, 1, hidden]) or an extend step (x [B, T, hidden]), B T <= 16 rows, on
+    ops.decode_linear: each norm runs inside the projection after it and the SwiGLU inside gate|up, with _layers'
+    rounding points. Per layer: norm + q|k|v, the cache append, the attention, the out projection, norm + gate|up +
+    SwiGLU, the down projection. decode_weights: the four projections read its Fp8Weights instead of the plan's
+    bf16 weights. Returns delta, residual as [B T, hidden]."""
     Hq, Hkv = model.num_heads, model.num_key_values
-    B = x.shape[0]
-    delta, residual = x.view(B, -1), None
+    B, T = x.shape[:2]
+    delta, residual = x.view(B * T, -1), None
     for i, (w_in, eps_in, w_qkv, w_out, w_post, eps_post, w_gu, w_down, cos, sin, kc, vc, ksc, vsc) in enumerate(plan):
         if decode_weights is not None:
             w_qkv, w_out, w_gu, w_down = decode_weights.layers[i]
         qkv, residual = ops.decode_linear(delta, w_qkv, norm_weight=w_in, eps=eps_in, residual=residual)
-        q = kv_cache_append(qkv.view(B, 1, -1), cos, sin, pos, kc, vc, Hq, Hkv, ksc, vsc)
-        o = ops.decode_linear(attend(q, kc, vc, ksc, vsc).view(B, -1), w_out)
+        q = kv_cache_append(qkv.view(B, T, -1), cos, sin, pos, kc, vc, Hq, Hkv, ksc, vsc)
+        o = ops.decode_linear(attend(q, kc, vc, ksc, vsc).view(B * T, -1), w_out)
         act, residual = ops.decode_linear(o, w_gu, norm_weight=w_post, eps=eps_post, residual=residual, swiglu=True)
         delta = ops.decode_linear(act, w_down)
     return delta, residual
@@ -647,6 +769,60 @@ def decode_step(model, tokens, cache, skinny_linear=False, decode_weights=None):
         delta, residual = _layers(model, plan, x, cache.lens, attend)
         logits = _head(model, delta[:, 0], residual[:, 0] if residual is not None else None)
     cache.lens += 1
+    return logits
+
+
+@torch.no_grad()
+def extend_step(model, tokens, cache, skinny_linear=False, decode_weights=None):
+    """T tokens per row in one pass over the weights: tokens int64 [B, T], 1 <= T <= 16 -> fp32 logits [B, T, V],
+    logits[:, t] being the next-token logits after tokens[:, t]; the cache grows by T. Positions are cache.lens on the
+    device: no host synchronisation, fixed shapes. Token t of a row attends to the cache and to tokens 0..t of the
+    call (attention_extend). With KVCache.rewind this is what verifying drafted tokens, continuing a cached
+    conversation by a few tokens, or scoring against a long cache needs; decode_step is the T = 1 case on its own
+    kernel (the two agree to rounding, not bit for bit).
+
+    Refused before anything is written: an FP8 KVCache (the extend kernel reads bf16 caches), T outside 1..16, a
+    cache shorter than T. Otherwise decode_step's rule for a full row holds: tokens past the end are skipped by the
+    append and attend to the full cache.
+
+    skinny_linear=True (B T <= 16 rows, refused beyond) and decode_weights: as in decode_step, over the B T rows."""
+    if tokens.dim() != 2:
+        raise ValueError("extend_step: tokens must be [batch, tokens]")
+    B, T = tokens.shape
+    if not 1 <= T <= MAX_EXTEND_TOKENS:
+        raise ValueError(f"extend_step: {T} tokens per row; 1 to {MAX_EXTEND_TOKENS} are supported (prefill takes a "
+                         "whole prompt)")
+    if decode_weights is not None:
+        _check_decode_weights(model, decode_weights, skinny_linear)
+    if skinny_linear:
+        if B * T > ops.DECODE_LINEAR_MAX_ROWS:
+            raise ValueError(f"extend_step: skinny_linear=True serves at most {ops.DECODE_LINEAR_MAX_ROWS} rows "
+                             f"(batch x tokens) per step, got {B} x {T}")
+        _check_skinny(model, B * T)
+    if isinstance(cache, KVCache) and cache.kv_dtype == _E4M3:
+        raise ValueError("extend_step: an FP8 KVCache is not supported (the extend kernel reads bf16 caches only)")
+    if isinstance(cache, KVCache) and cache.max_len < T:
+        raise ValueError(f"extend_step: the cache (max_len {cache.max_len}) is shorter than the {T} tokens")
+    plan = cache._plan if isinstance(cache, KVCache) and cache._plan_model is model else None
+    if plan is None:
+        _check_model(model)
+        _check_cache(model, cache, B)
+        plan = _layer_plan(model, cache, tokens.device)
+    elif cache.batch != B:
+        raise ValueError("generate: the cache does not fit this model / batch")
+    Hq, D = model.num_heads, model.head_dim
+    seqlens = cache.lens + T
+
+    def attend(q, kc, vc, ksc, vsc):
+        return attention_extend(q, kc, vc, seqlens).view(B, T, Hq * D)
+
+    x = torch.nn.functional.embedding(tokens, model.embedding.weight)
+    if skinny_linear:
+        logits = _head_skinny(model, *_layers_skinny(model, plan, x, cache.lens, attend, decode_weights),
+                              decode_weights).view(B, T, -1)
+    else:
+        logits = _head(model, *_layers(model, plan, x, cache.lens, attend))
+    cache.lens += T
     return logits
 
 
