@@ -624,6 +624,48 @@ int64_t pico_decode_linear_fp8_args_size(void);
 int pico_decode_linear_fp8_plan(int64_t m, int64_t n, int64_t k, int epilogue, int64_t split_k, int cus, int64_t* plan);
 int pico_decode_linear_fp8(const pico_decode_linear_fp8_args* args, void* stream);
 
+/* ---- Generation: MXFP4 (OCP e2m1, E8M0 block scales) weight-only skinny linear and its block quantiser ----
+ * A quantised weight is codes [n, k/2] bytes, two e2m1 codes each (element 2j the low nibble, 2j + 1 the high one),
+ *   plus scales [n, k/32] E8M0 bytes, block b of a row covering columns 32 b .. 32 b + 31: element (n, k) has the
+ *   value 2^(scales[n, k/32] - 127) * e2m1(code), e2m1 in +-{0, 0.5, 1, 1.5, 2, 3, 4, 6} (the sign is bit 3).
+ * pico_quantize_rows_mxfp4: w [n, k] bf16 (finite), row stride ldw elements -> codes with row stride ldc bytes and
+ *   scales with row stride lds bytes. Per block the shared exponent is e = floor(log2(absmax)) - 2 clamped to
+ *   [-120, 125] (a block of zeros: 0), the scale byte e + 127 (so 7 .. 252, and every dequantised value is a normal
+ *   bf16); a code is the round-to-nearest-even of |w| 2^-e on the e2m1 grid, saturated at 6, under w's sign bit.
+ *   Integer arithmetic on the bf16 bits: plain torch reproduces it bit for bit. k a multiple of 32, ldw of 8, ldc of
+ *   4; w 16-byte and codes 4-byte aligned. n == 0 is a no-op. Timed under PICO_K_CAST.
+ * pico_decode_linear_mxfp4: pico_decode_linear's contract on acc[m, n] = sum_k h[m, k] * value(n, k) in fp32 on the
+ *   matrix pipe; the block scale is applied by the conversion to bf16 (exact), so every product is exact and acc
+ *   takes its place in every epilogue as in pico_decode_linear: no scale afterwards, split-K partials are plain
+ *   sums. weight is the codes, ldw their row stride in bytes (a multiple of 16, the pointer 16-byte aligned);
+ *   weight_scale the scale bytes, lds their row stride in bytes (a multiple of 4, the pointer 4-byte aligned); scale
+ *   bytes 1 .. 254; k a multiple of 128. Everything else (m in 1..16, the norm prologue and the residual_out rule,
+ *   the other strides and alignments, split_k, determinism, row independence) is pico_decode_linear's.
+ * pico_decode_linear_mxfp4_plan: pico_decode_linear_fp8_plan's contract for this kernel: plan[0..3] = column blocks,
+ *   split_k, k_slice (a multiple of 128, at most 2048), workspace bytes; the host rule splits no finer than 1024
+ *   columns. Timed under PICO_K_DECODE_LINEAR. */
+typedef struct pico_decode_linear_mxfp4_args {
+  const void* x;
+  const void* weight;
+  const void* weight_scale;
+  void* y;
+  const void* norm_weight;
+  const void* residual;
+  void* residual_out;
+  void* workspace;
+  int64_t ldx, ldw, lds, ldy, ldr, ldro;
+  int64_t m, n, k;
+  int64_t split_k;
+  float eps;
+  int epilogue;
+} pico_decode_linear_mxfp4_args;
+int pico_quantize_rows_mxfp4(const void* w, int64_t ldw, void* codes, int64_t ldc, void* scales, int64_t lds,
+                             int64_t n, int64_t k, void* stream);
+int64_t pico_decode_linear_mxfp4_args_size(void);
+int pico_decode_linear_mxfp4_plan(int64_t m, int64_t n, int64_t k, int epilogue, int64_t split_k, int cus,
+                                  int64_t* plan);
+int pico_decode_linear_mxfp4(const pico_decode_linear_mxfp4_args* args, void* stream);
+
 /* ---- Generation: FP8 (OCP e4m3) KV cache: quantising append and decode attention ----
  * An FP8 cache is codes [batch, heads_kv, s_max, head_dim], one e4m3 byte each (finite codes only), with unit last
  *   stride and byte strides {batch, head, position} that are multiples of 8, plus scale [batch, heads_kv, s_max]

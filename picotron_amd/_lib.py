@@ -82,6 +82,17 @@ class DecodeLinearFp8Args(ctypes.Structure):
     ]
 
 
+class DecodeLinearMxfp4Args(ctypes.Structure):
+    """Mirror of `pico_decode_linear_mxfp4_args`."""
+    _fields_ = [
+        ("x", c_vp), ("weight", c_vp), ("weight_scale", c_vp), ("y", c_vp), ("norm_weight", c_vp), ("residual", c_vp),
+        ("residual_out", c_vp), ("workspace", c_vp),
+        ("ldx", c_i64), ("ldw", c_i64), ("lds", c_i64), ("ldy", c_i64), ("ldr", c_i64), ("ldro", c_i64),
+        ("m", c_i64), ("n", c_i64), ("k", c_i64), ("split_k", c_i64),
+        ("eps", ctypes.c_float), ("epilogue", ctypes.c_int),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "pico_abi_version": (ctypes.c_int, []),
@@ -170,6 +181,11 @@ _SIGNATURES = {
     "pico_decode_linear_fp8_plan": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, c_i64, ctypes.c_int,
                                                    ctypes.POINTER(c_i64)]),
     "pico_decode_linear_fp8": (ctypes.c_int, [ctypes.POINTER(DecodeLinearFp8Args), c_vp]),
+    "pico_quantize_rows_mxfp4": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "pico_decode_linear_mxfp4_args_size": (c_i64, []),
+    "pico_decode_linear_mxfp4_plan": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, c_i64, ctypes.c_int,
+                                                     ctypes.POINTER(c_i64)]),
+    "pico_decode_linear_mxfp4": (ctypes.c_int, [ctypes.POINTER(DecodeLinearMxfp4Args), c_vp]),
     "pico_kv_append_fp8": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
                                           c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64),
                                           c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64),

@@ -42,6 +42,8 @@ FILE_FLAGS = {
     "decode_linear.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # the same prologue and epilogues, and the quantiser's clamp: no packed fp32 VALU here either
     "decode_linear_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # the same prologue and epilogues again: no packed fp32 VALU
+    "decode_linear_mxfp4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # the online softmax and the rescale of the O^T accumulators beside the MFMAs: no packed fp32 VALU
     "attn_extend.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }

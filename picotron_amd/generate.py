@@ -23,6 +23,11 @@ conversation, scoring against a long cache): `kv_cache_append` with T tokens, th
 (`pico_attn_extend`: the T x Hq / Hkv query rows of a kv head on the matrix unit, split over the keys like the decode
 kernel, bf16 caches only). `KVCache.rewind` takes rejected tokens back on the device.
 
+`quantize_decode_weights(model, fmt)` snapshots the decode projections for `skinny_linear=True`: `fmt="fp8"` (e4m3
+codes, one fp32 scale per output row, `pico_decode_linear_fp8`) or `fmt="mxfp4"` (OCP e2m1 codes with one E8M0 scale
+byte per 32 columns, 4.25 bits per weight, `pico_decode_linear_mxfp4`); `decode_step`, `extend_step` and `generate`
+read either through `ops.decode_linear`.
+
 `sample_tokens` is the fused sampler (`pico_sample`: temperature, top-k, top-p, a Philox draw, the EOS / pad rule
 and the output column in one launch, every per-step value in a `SamplerState` on the device); with it a whole
 iteration, decode step and sampler, is captured once as a HIP graph and replayed per token (`generate(graph=True)`).
@@ -548,13 +553,18 @@ def _check_skinny(model, B):
 
 
 class DecodeWeights:
-    """The decode projections of a model as FP8 weights (ops.Fp8Weight: e4m3 codes, one fp32 scale per output row):
+    """The decode projections of a model as FP8 weights (ops.Fp8Weight: e4m3 codes, one fp32 scale per output row)
+    or as MXFP4 weights (ops.Mxfp4Weight: e2m1 codes, one E8M0 scale byte per 32 columns), one kind throughout:
     per layer the stacked q|k|v, out, the stacked gate|up and down, plus the LM head. Norm weights and the embedding
     are not part of it: they stay the model's bf16 parameters. A snapshot: it holds what the model's weights were
     when quantize_decode_weights ran and does not follow an optimizer step or a load_state_dict; quantise again."""
 
     def __init__(self, layers, head):
         self.layers, self.head = layers, head
+
+    @property
+    def fmt(self):
+        return "mxfp4" if isinstance(self.head, ops.Mxfp4Weight) else "fp8"
 
     def shapes(self):
         return [tuple(tuple(w.shape) for w in layer) for layer in self.layers] + [tuple(self.head.shape)]
@@ -573,13 +583,17 @@ def _decode_shapes(model):
 
 
 @torch.no_grad()
-def quantize_decode_weights(model):
+def quantize_decode_weights(model, fmt="fp8"):
     """DecodeWeights of `model`: every decode projection quantised once by ops.quantize_weight_fp8 (the stacked
     q|k|v and gate|up as the stacked views ops.stacked_weight gives, without a bf16 copy). Pass the result as
     decode_step / generate's decode_weights (with skinny_linear=True). It is a snapshot of the weights as they are
-    now, half the bytes of the bf16 projections plus 4 bytes per output row."""
+    now, half the bytes of the bf16 projections plus 4 bytes per output row. fmt="mxfp4": by
+    ops.quantize_weight_mxfp4 instead, a quarter of the bf16 bytes plus one scale byte per 32 weights (every
+    projection's K must be a multiple of 32 to quantise, of 128 to decode)."""
     _check_model(model)
-    q = ops.quantize_weight_fp8
+    if fmt not in ("fp8", "mxfp4"):
+        raise ValueError(f"quantize_decode_weights: fmt is 'fp8' or 'mxfp4', got {fmt!r}")
+    q = ops.quantize_weight_fp8 if fmt == "fp8" else ops.quantize_weight_mxfp4
     layers = []
     for layer in model.decoder_layers:
         a, f = layer.attention, layer.mlp
@@ -590,7 +604,7 @@ def quantize_decode_weights(model):
 
 def _check_decode_weights(model, w, skinny_linear):
     """decode_weights is refused without skinny_linear, for another model's shapes, and where ops.decode_linear
-    would refuse a projection (an Fp8Weight needs K to be a multiple of 64)."""
+    would refuse a projection (an Fp8Weight needs K to be a multiple of 64, an Mxfp4Weight of 128)."""
     if not skinny_linear:
         raise ValueError("generate: decode_weights belongs to skinny_linear=True (the FP8 weights are read by "
                          "ops.decode_linear alone)")
@@ -598,6 +612,12 @@ def _check_decode_weights(model, w, skinny_linear):
         raise ValueError("generate: decode_weights does not fit this model (quantize_decode_weights(model) makes it)")
     *layers, head = w.shapes()
     bad = sorted({k for layer in layers for _, k in layer} | {head[1]})
+    if w.fmt == "mxfp4":
+        bad = [f"K = {k}" for k in bad if k % 128]
+        if bad:
+            raise ValueError("generate: MXFP4 decode_weights need every projection's K to be a multiple of 128 "
+                             f"(ops.decode_linear with an Mxfp4Weight): {', '.join(bad)}")
+        return
     bad = [f"K = {k}" for k in bad if k % 64]
     if bad:
         raise ValueError("generate: decode_weights needs every projection's K to be a multiple of 64 "
@@ -608,8 +628,8 @@ def _layers_skinny(model, plan, x, pos, attend, decode_weights=None):
     """_layers for a decode step (x [B, 1, hidden]) or an extend step (x [B, T, hidden]), B T <= 16 rows, on
     ops.decode_linear: each norm runs inside the projection after it and the SwiGLU inside gate|up, with _layers'
     rounding points. Per layer: norm + q|k|v, the cache append, the attention, the out projection, norm + gate|up +
-    SwiGLU, the down projection. decode_weights: the four projections read its Fp8Weights instead of the plan's
-    bf16 weights. Returns delta, residual as [B T, hidden]."""
+    SwiGLU, the down projection. decode_weights: the four projections read its Fp8Weights (or Mxfp4Weights) instead
+    of the plan's bf16 weights. Returns delta, residual as [B T, hidden]."""
     Hq, Hkv = model.num_heads, model.num_key_values
     B, T = x.shape[:2]
     delta, residual = x.view(B * T, -1), None

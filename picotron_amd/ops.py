@@ -1468,9 +1468,15 @@ def decode_linear(x, weight, *, norm_weight=None, eps=None, residual=None, swigl
 
     weight may be an Fp8Weight (ops.quantize_weight_fp8): e4m3 codes and one fp32 scale per output row. The products
     h * e4m3(code) are accumulated in fp32 and scale[n] * acc, one fp32 multiply, takes acc's place in every
-    epilogue (pico_decode_linear_fp8); K must then be a multiple of 64. Every other argument keeps its meaning."""
+    epilogue (pico_decode_linear_fp8); K must then be a multiple of 64. Every other argument keeps its meaning.
+
+    weight may be an Mxfp4Weight (ops.quantize_weight_mxfp4): e2m1 codes and one E8M0 scale byte per 32 columns. The
+    block scale is applied when the codes become bf16 (exactly), so acc is the plain fp32 sum of exact products and
+    every epilogue is pico_decode_linear's (pico_decode_linear_mxfp4); K must then be a multiple of 128."""
     if isinstance(weight, Fp8Weight):
         return _decode_linear_fp8(x, weight, norm_weight, eps, residual, swiglu, out_dtype, split_k)
+    if isinstance(weight, Mxfp4Weight):
+        return _decode_linear_mxfp4(x, weight, norm_weight, eps, residual, swiglu, out_dtype, split_k)
     if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
         raise ValueError(f"decode_linear: x {tuple(x.shape)} and weight {tuple(weight.shape)} must be [M, K] and [N, K]")
     M, K = x.shape
@@ -1640,6 +1646,148 @@ def _decode_linear_fp8(x, weight, norm_weight, eps, residual, swiglu, out_dtype,
     a.ldr, a.ldro = (residual.stride(0), K) if residual is not None else (0, 0)
     a.m, a.n, a.k, a.split_k, a.eps, a.epilogue = M, N, K, sk, eps, epi
     _lib.check(lib.pico_decode_linear_fp8(ctypes.byref(a), _lib.stream_of(x)), "pico_decode_linear_fp8")
+    if norm_weight is None:
+        return y
+    return y, (res_out if res_out is not None else x)
+
+
+# --------------------------------------------------------------------------------------------
+# MXFP4 (OCP e2m1 codes, E8M0 block scales) weight-only skinny linear: csrc/decode_linear_mxfp4.hip
+# --------------------------------------------------------------------------------------------
+MX_BLOCK = 32  # elements per E8M0 scale byte (csrc/decode_linear_mxfp4_plan.h MX4_BLOCK)
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# |v| between grid values i and i + 1 rounds up past their midpoint; on it, to the even code
+_E2M1_MID = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)
+
+
+class Mxfp4Weight:
+    """An MXFP4 weight: codes [N, K/2] uint8, two e2m1 codes per byte (element 2j the low nibble, 2j + 1 the high
+    one), and scales [N, K/32] uint8 E8M0 bytes, block b covering columns 32 b .. 32 b + 31; element (n, k) has the
+    value 2^(scales[n, k // 32] - 127) * e2m1(code). Rows of two Mxfp4Weights concatenate into the stacked matrix's."""
+    __slots__ = ("codes", "scales")
+
+    def __init__(self, codes, scales):
+        if codes.dim() != 2 or codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.shape[1] % 16 or \
+                scales.shape != (codes.shape[0], codes.shape[1] // 16) or scales.device != codes.device:
+            raise ValueError("Mxfp4Weight: codes [N, K/2] uint8 and scales [N, K/32] uint8 on one device, K a "
+                             "multiple of 32")
+        self.codes, self.scales = codes, scales
+
+    @property
+    def shape(self):
+        return torch.Size((self.codes.shape[0], 2 * self.codes.shape[1]))
+
+    def dequantize(self, dtype=torch.float32):
+        """2^(scale - 127) * e2m1(code): a two-bit significand, exact in fp32 and, for scale bytes the quantiser
+        writes (7 .. 252), in bf16."""
+        c = self.codes.long()
+        idx = torch.stack((c & 15, c >> 4), -1).flatten(1)  # [N, K] codes in column order
+        lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32, device=c.device)
+        e = self.scales.to(torch.int32).repeat_interleave(MX_BLOCK, 1) - 127
+        return torch.ldexp(lut[idx], e).to(dtype)
+
+
+def _quantize_blocks_cpu(wf):
+    """quantize_weight_mxfp4's arithmetic on fp32 rows [N, K] (bf16 values) in plain torch: (codes, scales)."""
+    N, K = wf.shape
+    blk = wf.view(N, K // MX_BLOCK, MX_BLOCK)
+    a = blk.abs().amax(-1)
+    e = (torch.frexp(a).exponent - 3).clamp(-120, 125)  # a = m 2^x, m in [0.5, 1): floor(log2 a) - 2 = x - 3
+    e = torch.where(a == 0, torch.zeros_like(e), e)
+    v = torch.ldexp(blk, -e[..., None]).abs()  # exact: a power-of-two scaling of a bf16 value within fp32's range
+    code = torch.zeros_like(v, dtype=torch.int32)
+    for i, mid in enumerate(_E2M1_MID):
+        code += (v >= mid) if i % 2 else (v > mid)  # saturates at 7 (6.0) by running out of midpoints
+    code |= torch.signbit(blk).to(torch.int32) << 3
+    code = code.view(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8), (e + 127).to(torch.uint8)
+
+
+def quantize_weight_mxfp4(weight):
+    """Mxfp4Weight of a bf16 weight [N, K] (or of the tuple ops.stacked_weight takes: the stacked view is quantised,
+    no bf16 copy), K a multiple of 32, by the OCP MX rule: per block of 32 columns the shared exponent e =
+    floor(log2(absmax)) - 2 clamped to [-120, 125] (a block of zeros: 0), scale byte e + 127; a code is the
+    round-to-nearest-even of w 2^-e on the e2m1 grid, saturated at +-6, with w's sign bit. HIP tensors take
+    pico_quantize_rows_mxfp4, CPU tensors the same arithmetic in plain torch, bit for bit. The weight must be
+    finite."""
+    w = stacked_weight(tuple(weight)) if isinstance(weight, (tuple, list)) else weight.detach()
+    if w.dim() != 2 or w.dtype != _BF16 or w.stride(1) != 1:
+        raise ValueError("quantize_weight_mxfp4: weight must be a bf16 [N, K] matrix with unit last stride")
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"quantize_weight_mxfp4: K = {K} must be a multiple of {MX_BLOCK} (one scale per block)")
+    if w.device.type == "cpu":
+        return Mxfp4Weight(*_quantize_blocks_cpu(w.float()))
+    _need(w, "weight")
+    if w.stride(0) % 8:
+        raise ValueError("quantize_weight_mxfp4: the row stride must be a multiple of 8")
+    codes = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((N, K // MX_BLOCK), dtype=torch.uint8, device=w.device)
+    _lib.check(_lib.load().pico_quantize_rows_mxfp4(w.data_ptr(), w.stride(0), codes.data_ptr(), K // 2,
+                                                    scales.data_ptr(), K // MX_BLOCK, N, K, _lib.stream_of(w)),
+               "pico_quantize_rows_mxfp4")
+    return Mxfp4Weight(codes, scales)
+
+
+def _decode_linear_mxfp4(x, weight, norm_weight, eps, residual, swiglu, out_dtype, split_k):
+    """ops.decode_linear for an Mxfp4Weight: the same checks, then pico_decode_linear_mxfp4 or the restatement."""
+    codes, scales = weight.codes, weight.scales
+    N, K = weight.shape
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"decode_linear: x {tuple(x.shape)} and weight {(N, K)} must be [M, K] and [N, K]")
+    M = x.shape[0]
+    if not 1 <= M <= DECODE_LINEAR_MAX_ROWS:
+        raise ValueError(f"decode_linear: {M} rows; 1..{DECODE_LINEAR_MAX_ROWS} are supported (a decode step's batch)")
+    if K % 128 or N % (16 if swiglu else 8):
+        raise ValueError(f"decode_linear: with an Mxfp4Weight K = {K} must be a multiple of 128 and N = {N} of "
+                         f"{16 if swiglu else 8}")
+    out_dtype = _BF16 if out_dtype is None else out_dtype
+    if out_dtype not in (_BF16, torch.float32) or (swiglu and out_dtype != _BF16):
+        raise ValueError("decode_linear: out_dtype is bfloat16, or float32 without swiglu")
+    if norm_weight is None and (residual is not None or eps is not None):
+        raise ValueError("decode_linear: residual / eps belong to the norm prologue (norm_weight is None)")
+    if norm_weight is not None and (norm_weight.shape != (K,) or not norm_weight.is_contiguous()):
+        raise ValueError(f"decode_linear: norm_weight must be a contiguous [{K}] tensor")
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("decode_linear: residual must have x's shape")
+    for t, n in ((x, "x"), (residual, "residual")):
+        if t is not None and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < K):
+            raise ValueError(f"decode_linear: {n} needs unit last stride and a row stride that is a multiple of 8")
+    if codes.stride(1) != 1 or codes.stride(0) % 16 or scales.stride(1) != 1 or scales.stride(0) % 4 or \
+            codes.device != x.device:
+        raise ValueError("decode_linear: the Mxfp4Weight's codes and scales need unit last stride and row strides "
+                         "that are multiples of 16 and 4 bytes, and x's device")
+    if split_k is not None and int(split_k) <= 0:
+        raise ValueError("decode_linear: split_k must be positive")
+    eps = 1e-5 if eps is None else float(eps)
+    if x.device.type == "cpu" or x.dtype != _BF16:
+        y, res_out = _decode_linear_reference(x, weight.dequantize(), norm_weight, eps, residual, swiglu, out_dtype)
+        if norm_weight is None:
+            return y
+        return y, (res_out if res_out is not None else x)
+    from .generate import _workspace
+    for t, n in ((x, "x"), (norm_weight, "norm_weight"), (residual, "residual")):
+        if t is not None:
+            _need(t, n)
+    lib = _lib.load()
+    epi = _lib.DL_SWIGLU if swiglu else (_lib.DL_F32 if out_dtype == torch.float32 else _lib.DL_BF16)
+    sk = 0 if split_k is None else int(split_k)
+    plan = (ctypes.c_int64 * 4)()
+    if lib.pico_decode_linear_mxfp4_plan(M, N, K, epi, sk, 0, plan):
+        raise ValueError("decode_linear: " + lib.pico_last_error().decode(errors="replace"))
+    ws = _workspace(x.device, plan[3]) if plan[3] else None
+    y = torch.empty((M, N // 2 if swiglu else N), dtype=out_dtype, device=x.device)
+    res_out = torch.empty((M, K), dtype=_BF16, device=x.device) if residual is not None else None
+    a = _lib.DecodeLinearMxfp4Args()
+    a.x, a.weight, a.weight_scale, a.y = x.data_ptr(), codes.data_ptr(), scales.data_ptr(), y.data_ptr()
+    a.norm_weight = norm_weight.data_ptr() if norm_weight is not None else None
+    a.residual = residual.data_ptr() if residual is not None else None
+    a.residual_out = res_out.data_ptr() if res_out is not None else None
+    a.workspace = ws.data_ptr() if ws is not None else None
+    a.ldx, a.ldw, a.lds, a.ldy = x.stride(0), codes.stride(0), scales.stride(0), y.stride(0)
+    a.ldr, a.ldro = (residual.stride(0), K) if residual is not None else (0, 0)
+    a.m, a.n, a.k, a.split_k, a.eps, a.epilogue = M, N, K, sk, eps, epi
+    _lib.check(lib.pico_decode_linear_mxfp4(ctypes.byref(a), _lib.stream_of(x)), "pico_decode_linear_mxfp4")
     if norm_weight is None:
         return y
     return y, (res_out if res_out is not None else x)

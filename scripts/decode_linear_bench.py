@@ -11,13 +11,15 @@ of a peak. Kernel times come from a kernel trace:
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/decode_linear_bench.py trace
   python scripts/decode_linear_bench.py table --trace DIR/.../*_kernel_trace.csv [--out profiles/...jsonl]
 
-`trace` quantises every weight of the ring once (ops.quantize_weight_fp8), warms every form up, then runs, per shape
-and M, a marker launch (pico_scale_f32), --iters decode_linear calls, a marker, --iters F.linear calls (the GEMM
-alone: what hipBLASLt launches for the shape), a marker, --iters decode_linear calls on the Fp8Weights; nothing else
-runs on the device in between. `table` cuts the trace at the markers and reports, per shape and M, the median kernel
+`trace` quantises every weight of the ring once (ops.quantize_weight_fp8, ops.quantize_weight_mxfp4), warms every
+form up, then runs, per shape and M, a marker launch (pico_scale_f32), --iters decode_linear calls, a marker, --iters
+F.linear calls (the GEMM alone: what hipBLASLt launches for the shape), a marker, --iters decode_linear calls on the
+Fp8Weights, a marker, --iters decode_linear calls on the Mxfp4Weights (their ring filled up with clones to the bf16
+ring's bytes, so that it does not fit the last-level cache either); nothing else runs on the device in between. `table` cuts the trace at the markers and reports, per shape and M, the median kernel
 time per call of the stream kernel, of the finishing launch and of hipBLASLt's kernels, with the weight's bytes over
-the stream + finish time as a share of the HBM peak; the same for the FP8 kernels (share on the FP8 bytes, N K), and
-the quantiser's time per matrix.
+the stream + finish time as a share of the HBM peak; the same for the FP8 kernels (share on the FP8 bytes, N K) and the
+MXFP4 kernels (share on N K / 2 + N K / 32 bytes, and their time over the FP8 kernels'), and the quantisers' time per
+matrix.
 
 Usage: python scripts/decode_linear_bench.py [calls|trace|table] [--out FILE] [--iters 40] [--rounds 3] [--trace CSV]
 """
@@ -138,6 +140,22 @@ def trace(args):
         kw = dict(norm_weight=gamma[K], eps=1e-5, residual=res) if norm else {}
         ops.decode_linear(x, q8[name][i % len(ws)], swiglu=swiglu, out_dtype=torch.float32 if f32 else None, **kw)
 
+    # ... and as MXFP4; that ring is filled up with clones until it, too, is RING_BYTES of codes and scales: the
+    # quantised copies alone (17 / 64 of the bf16 bytes) would fit the last-level cache
+    q4 = {}
+    for c in cases:
+        if c[0] not in q4:
+            q4[c[0]] = ring = [ops.quantize_weight_mxfp4(w) for w in c[7]]
+            each = ring[0].codes.numel() + ring[0].scales.numel()
+            for j in range(RING_BYTES // each + 1 - len(ring)):
+                ring.append(ops.Mxfp4Weight(ring[j % len(c[7])].codes.clone(), ring[j % len(c[7])].scales.clone()))
+
+    def mx4(c, i):
+        name, N, K, norm, swiglu, f32, M, ws = c
+        x, res = xs[(name, M)]
+        kw = dict(norm_weight=gamma[K], eps=1e-5, residual=res) if norm else {}
+        ops.decode_linear(x, q4[name][i % len(q4[name])], swiglu=swiglu, out_dtype=torch.float32 if f32 else None, **kw)
+
     def marker():
         _lib.check(lib.pico_scale_f32(_lib.ptr(mark), mark.numel(), 2.0, _lib.stream_of(mark)), "pico_scale_f32")
 
@@ -147,9 +165,10 @@ def trace(args):
                 skinny(c, i)
                 gemm(c, i)
                 fp8(c, i)
+                mx4(c, i)
         torch.cuda.synchronize()
         for c in cases:
-            for fn in (skinny, gemm, fp8):
+            for fn in (skinny, gemm, fp8, mx4):
                 marker()
                 for i in range(args.iters):
                     fn(c, i)
@@ -170,16 +189,23 @@ def table(args):
             cur.append((r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
     segs = segs[:-1]  # the closing marker opens nothing
     combos = [(s[0], s[1], s[2], M) for s in SHAPES for M in (1, 8)]
-    assert len(segs) == 3 * len(combos), (len(segs), len(combos))
+    assert len(segs) == 4 * len(combos), (len(segs), len(combos))
     med = lambda v: sorted(v)[len(v) // 2] if v else 0.0
     quant = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows
              if "quantize_rows_fp8" in r["Kernel_Name"]]
-    quant_us = {}
+    quant4 = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows
+              if "quantize_rows_mxfp4" in r["Kernel_Name"]]
+    quant_us, quant4_us = {}, {}
     for name, N, K, *_ in SHAPES:  # one launch per matrix of the ring, shape after shape
         copies = max(2, RING_BYTES // (N * K * 2) + 1)
         quant_us[name], quant = round(med(quant[:copies]), 2), quant[copies:]
+        quant4_us[name], quant4 = round(med(quant4[:copies]), 2), quant4[copies:]
     for i, (name, N, K, M) in enumerate(combos):
-        ours, theirs, eight = segs[3 * i], segs[3 * i + 1], segs[3 * i + 2]
+        ours, theirs, eight, four = segs[4 * i:4 * i + 4]
+        stream4 = [t for n, t in four if "decode_linear_mxfp4_kernel" in n]
+        finish4 = [t for n, t in four if "decode_linear_mxfp4_finish" in n]
+        assert len(stream4) + len(finish4) == len(four) and len(stream4) == args.iters, (name, M, len(four))
+        total4 = med(stream4) + med(finish4)
         stream8 = [t for n, t in eight if "decode_linear_fp8_kernel" in n]
         finish8 = [t for n, t in eight if "decode_linear_fp8_finish" in n]
         assert len(stream8) + len(finish8) == len(eight) and len(stream8) == args.iters, (name, M, len(eight))
@@ -199,7 +225,11 @@ def table(args):
                "hipblaslt_kernel": theirs[0][0][:80],
                "fp8_stream_us": round(med(stream8), 2), "fp8_finish_us": round(med(finish8), 2),
                "fp8_us": round(total8, 2), "fp8_hbm_share": round(share(total8) / 2, 3),  # on the FP8 bytes: N K
-               "fp8_over_bf16": round(total8 / total, 3), "quantize_us": quant_us[name]}
+               "fp8_over_bf16": round(total8 / total, 3), "quantize_us": quant_us[name],
+               "mxfp4_stream_us": round(med(stream4), 2), "mxfp4_finish_us": round(med(finish4), 2),
+               "mxfp4_us": round(total4, 2),  # the share on the MXFP4 bytes: N K / 2 + N K / 32
+               "mxfp4_hbm_share": round(share(total4) * (0.5 + 1 / 32) / 2, 3),
+               "mxfp4_over_fp8": round(total4 / total8, 3), "quantize_mxfp4_us": quant4_us[name]}
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:

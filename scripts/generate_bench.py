@@ -18,7 +18,11 @@ device; reads nothing outside the repository.
            skinny_linear=True, FP8 decode weights), with the bf16 KV cache and with the FP8 KV cache
            (kv_dtype=torch.float8_e4m3fn), alternated; the decode step is (whole call - prefill) / 127.
 
-Usage: python scripts/generate_bench.py sampler|e2e|e2e_long [--out profiles/generate_bench.jsonl] [--iters 200] [--rounds 3]
+  e2e_mxfp4 the e2e geometry on graph=True, skinny_linear=True with FP8 and with MXFP4 decode weights
+           (quantize_decode_weights(model, fmt="mxfp4")), greedy, alternated in one process: ms per generated token,
+           the rounds, their spread and the ratio.
+
+Usage: python scripts/generate_bench.py sampler|e2e|e2e_long|e2e_mxfp4 [--out profiles/generate_bench.jsonl] [--iters 200] [--rounds 3]
 """
 import argparse
 import json
@@ -251,9 +255,52 @@ def e2e_long(args):
         _emit(args, rec)
 
 
+def e2e_mxfp4(args):
+    from picotron_amd import generate as G
+    from picotron_amd.model import build_llama, smollm_1_7b
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    cfg = smollm_1_7b(num_hidden_layers=args.layers, seq_length=2048)
+    torch.manual_seed(0)
+    model = build_llama(cfg, device=dev)
+    with torch.no_grad():
+        model.final_proj.weight.normal_(0.0, 0.02)
+    sets = {"fp8": G.quantize_decode_weights(model), "mxfp4": G.quantize_decode_weights(model, fmt="mxfp4")}
+    P, N = 128, 128
+    for B in (1, 8):
+        prompt = torch.randint(0, cfg.vocab_size, (B, P), generator=torch.Generator().manual_seed(B)).to(dev)
+        caches = {name: G.KVCache(model, B, P + N) for name in sets}  # a cache holds one captured graph
+        forms = {name: (lambda name=name: G.generate(model, prompt, N, cache=caches[name], graph=True,
+                                                     skinny_linear=True, decode_weights=sets[name]))
+                 for name in sets}
+
+        def prefill_only():
+            caches["fp8"].reset()
+            G.prefill(model, prompt, caches["fp8"])
+
+        forms["prefill"] = prefill_only
+        for name, fn in forms.items():
+            _clock_ms(fn)
+            _log(f"B={B} warm {name} done")
+        ms = {name: [] for name in forms}
+        for _ in range(args.rounds):
+            for name, fn in forms.items():
+                ms[name].append(_clock_ms(fn))
+        med = {name: _median(x) for name, x in ms.items()}
+        rec = {"mode": "e2e_mxfp4", "model": f"SmolLM-1.7B geometry, {args.layers} layers", "B": B, "prompt": P,
+               "new_tokens": N, "route": "graph + skinny_linear, greedy", "prefill_ms": round(med["prefill"], 3)}
+        for name in sets:
+            rec[name + "_ms_rounds"] = [round(x, 1) for x in ms[name]]
+            rec[name + "_ms_per_token"] = round(med[name] / N, 3)
+            rec[name + "_decode_step_ms"] = round((med[name] - med["prefill"]) / (N - 1), 4)
+        rec["mxfp4_over_fp8"] = round(med["mxfp4"] / med["fp8"], 3)
+        rec["spread_ms"] = round(max(max(v) - min(v) for k, v in ms.items() if k in sets), 1)
+        _emit(args, rec)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["sampler", "e2e", "e2e_long"])
+    ap.add_argument("mode", choices=["sampler", "e2e", "e2e_long", "e2e_mxfp4"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generate_bench.jsonl"),
                     help="append the JSON lines to this file")
     ap.add_argument("--iters", type=int, default=200)
@@ -262,4 +309,4 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("generate_bench: needs a HIP device (no measurement without one)")
-    {"sampler": sampler, "e2e": e2e, "e2e_long": e2e_long}[a.mode](a)
+    {"sampler": sampler, "e2e": e2e, "e2e_long": e2e_long, "e2e_mxfp4": e2e_mxfp4}[a.mode](a)
