@@ -239,6 +239,18 @@ int pico_attn_fwd(const pico_attn_args* args, void* stream);
 int64_t pico_attn_bwd_workspace_bytes(const pico_attn_args* args);
 int pico_attn_bwd(const pico_attn_args* args, void* stream);
 
+/* Document-masked causal attention of packed rows (several documents per row): query i of row b sees key j iff
+ * doc_start[b][i] <= j <= i. doc_bounds: int32 [2][B][S] contiguous, plane 0 = doc_start (the first token of the
+ * document that holds each token), plane 1 = doc_end (one past its last token); positions for RoPE stay the
+ * sequence index. The kernels clamp start into [0, i] and end into [j + 1, S], so bad bounds give wrong numbers,
+ * never a bad address. Same pico_attn_args, flags and layouts as the plain entry points; refused (status 1000)
+ * besides what those refuse: null doc_bounds, causal == 0, seqlen_q != seqlen_k. The backward always runs the
+ * 32-row dK/dV kernel (PICO_SEL_ATTN_KVP is ignored); its workspace is pico_attn_doc_bwd_workspace_bytes. Timed
+ * under the ids of the plain kernels (PICO_K_ATTN_FWD, _BWD_Q, _BWD_KV, _BWD_DKV). */
+int pico_attn_doc_fwd(const pico_attn_args* args, const void* doc_bounds, void* stream);
+int64_t pico_attn_doc_bwd_workspace_bytes(const pico_attn_args* args);
+int pico_attn_doc_bwd(const pico_attn_args* args, const void* doc_bounds, void* stream);
+
 /* ---- ring-attention block merge (update_out_and_lse) ----
  * ref picotron/context_parallel/context_parallel.py:157-187:
  *   first != 0: out = float(block_out), lse = block_lse

@@ -121,6 +121,9 @@ _SIGNATURES = {
     "pico_attn_fwd": (ctypes.c_int, [ctypes.POINTER(AttnArgs), c_vp]),
     "pico_attn_bwd_workspace_bytes": (c_i64, [ctypes.POINTER(AttnArgs)]),
     "pico_attn_bwd": (ctypes.c_int, [ctypes.POINTER(AttnArgs), c_vp]),
+    "pico_attn_doc_fwd": (ctypes.c_int, [ctypes.POINTER(AttnArgs), c_vp, c_vp]),
+    "pico_attn_doc_bwd_workspace_bytes": (c_i64, [ctypes.POINTER(AttnArgs)]),
+    "pico_attn_doc_bwd": (ctypes.c_int, [ctypes.POINTER(AttnArgs), c_vp, c_vp]),
     "pico_attn_merge": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
                                        ctypes.POINTER(c_i64), ctypes.c_int, c_vp, ctypes.POINTER(c_i64), c_i64, c_i64,
                                        c_i64, c_i64, ctypes.c_int, c_vp]),

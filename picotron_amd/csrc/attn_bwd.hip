@@ -12,8 +12,8 @@
 // picotron_hip.h so the profiling ids of the others do not move.
 #include "attn_common.h"
 
-int64_t pico_attn_bwd_split_workspace(const pico_attn_args* a);
-int pico_attn_bwd_split(const pico_attn_args* a, hipStream_t s);
+int64_t pico_attn_bwd_split_workspace(const pico_attn_args* a, bool doc);
+int pico_attn_bwd_split(const pico_attn_args* a, hipStream_t s, const int* doc);
 
 // Shared argument validation for forward and backward.
 int pico_attn_check_common(const pico_attn_args* a, const char* op) {
@@ -35,31 +35,58 @@ int pico_attn_check_common(const pico_attn_args* a, const char* op) {
   return 0;
 }
 
+// What the document-masked entry points add to the shared validation: the bounds, and a causal self-attention shape.
+int pico_attn_check_doc(const pico_attn_args* a, const void* doc_bounds, const char* op) {
+  int rc = pico_attn_check_common(a, op);
+  if (rc) return rc;
+  PICO_REQUIRE(doc_bounds, "%s: null doc_bounds", op);
+  PICO_REQUIRE((uintptr_t)doc_bounds % 4 == 0, "%s: doc_bounds must be 4-byte aligned", op);
+  PICO_REQUIRE(a->causal, "%s: the document mask is causal (causal == 0)", op);
+  PICO_REQUIRE(a->seqlen_q == a->seqlen_k, "%s: the document mask needs seqlen_q == seqlen_k", op);
+  return 0;
+}
+
+// the checks of pico_attn_bwd after the shape checks (op names the entry point in the messages); doc = the
+// document bounds of pico_attn_doc_bwd, or null
+static int attn_bwd_entry(const pico_attn_args* a, const int* doc, void* stream, const char* op) {
+  PICO_REQUIRE(a->o && a->lse && a->dout && a->dq && a->dk && a->dv && a->workspace, "%s: null pointer", op);
+  const int64_t* st[5] = {a->o_strides, a->do_strides, a->dq_strides, a->dk_strides, a->dv_strides};
+  for (int i = 0; i < 5; ++i)
+    for (int d = 0; d < 3; ++d)
+      PICO_REQUIRE(st[i][d] % 8 == 0 || (i == 2 && (a->flags & PICO_ATTN_DQ_F32_ACCUM)),
+                   "%s: strides must be multiples of 8 elements", op);
+  if (a->flags & PICO_ATTN_ROPE_BWD) {
+    PICO_REQUIRE(!(a->flags & PICO_ATTN_DQ_F32_ACCUM), "%s: ROPE_BWD cannot be combined with DQ_F32_ACCUM", op);
+    PICO_REQUIRE(a->rope_cos && a->rope_sin && ((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin) % 16 == 0,
+                 "%s: ROPE_BWD needs 16-byte aligned cos/sin tables", op);
+    PICO_REQUIRE(a->rope_stride % 8 == 0 && a->rope_stride >= a->head_dim / 2,
+                 "%s: bad rope table row stride %lld", op, (long long)a->rope_stride);
+  }
+  if (a->batch == 0 || a->seqlen_q == 0 || a->heads_q == 0) return 0;
+  return pico_attn_bwd_split(a, (hipStream_t)stream, doc);
+}
+
 extern "C" {
 
 int64_t pico_attn_args_size(void) { return (int64_t)sizeof(pico_attn_args); }
 
 // [lse2 | delta] each [B*Hq][Sq padded to 32] fp32, + fp32 dK/dV partials when a small grid splits key blocks
-int64_t pico_attn_bwd_workspace_bytes(const pico_attn_args* a) { return pico_attn_bwd_split_workspace(a); }
+int64_t pico_attn_bwd_workspace_bytes(const pico_attn_args* a) { return pico_attn_bwd_split_workspace(a, false); }
 
 int pico_attn_bwd(const pico_attn_args* a, void* stream) {
   int rc = pico_attn_check_common(a, "pico_attn_bwd");
   if (rc) return rc;
-  PICO_REQUIRE(a->o && a->lse && a->dout && a->dq && a->dk && a->dv && a->workspace, "pico_attn_bwd: null pointer");
-  const int64_t* st[5] = {a->o_strides, a->do_strides, a->dq_strides, a->dk_strides, a->dv_strides};
-  for (int i = 0; i < 5; ++i)
-    for (int d = 0; d < 3; ++d)
-      PICO_REQUIRE(st[i][d] % 8 == 0 || (i == 2 && (a->flags & PICO_ATTN_DQ_F32_ACCUM)),
-                   "pico_attn_bwd: strides must be multiples of 8 elements");
-  if (a->flags & PICO_ATTN_ROPE_BWD) {
-    PICO_REQUIRE(!(a->flags & PICO_ATTN_DQ_F32_ACCUM), "pico_attn_bwd: ROPE_BWD cannot be combined with DQ_F32_ACCUM");
-    PICO_REQUIRE(a->rope_cos && a->rope_sin && ((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin) % 16 == 0,
-                 "pico_attn_bwd: ROPE_BWD needs 16-byte aligned cos/sin tables");
-    PICO_REQUIRE(a->rope_stride % 8 == 0 && a->rope_stride >= a->head_dim / 2,
-                 "pico_attn_bwd: bad rope table row stride %lld", (long long)a->rope_stride);
-  }
-  if (a->batch == 0 || a->seqlen_q == 0 || a->heads_q == 0) return 0;
-  return pico_attn_bwd_split(a, (hipStream_t)stream);
+  return attn_bwd_entry(a, nullptr, stream, "pico_attn_bwd");
+}
+
+// Document-masked causal attention of packed rows (the forward is in attn_fwd.hip): the same arguments plus
+// doc_bounds = ops.doc_bounds, int32 [2][B][S]; the plan takes the 32-row dK/dV kernel (attn_bwd_plan.h split_plan).
+int64_t pico_attn_doc_bwd_workspace_bytes(const pico_attn_args* a) { return pico_attn_bwd_split_workspace(a, true); }
+
+int pico_attn_doc_bwd(const pico_attn_args* a, const void* doc_bounds, void* stream) {
+  int rc = pico_attn_check_doc(a, doc_bounds, "pico_attn_doc_bwd");
+  if (rc) return rc;
+  return attn_bwd_entry(a, (const int*)doc_bounds, stream, "pico_attn_doc_bwd");
 }
 
 }  // extern "C"

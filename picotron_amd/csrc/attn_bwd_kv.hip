@@ -31,14 +31,20 @@ struct KVCfg {
   static constexpr int NPW = (NP + KNW - 1) / KNW;
 };
 
-template <int D, bool CAUSAL, int MINB>
+// DOC (pico_attn_doc_bwd): `doc` is the document bounds, int32 [2][B][Sq]; this kernel reads plane 1, the ends:
+// key j is seen by the queries j <= i < end[b][j]. Each lane clamps its key's end into [key + 1, Sq]; `row >= end`
+// joins the causal test in the C-operand mask, on every tile that reaches the end of the wave's first key; the
+// block's query-tile list ends at the end of its last valid key (workgroup-uniform, in an SGPR), so an hsplit
+// share may be left with no tile: it runs no DMA and writes zero partials, which attn_bwd_dkv_kernel adds.
+template <int D, bool CAUSAL, int MINB, bool DOC = false>
 __global__ __launch_bounds__(KNW * 64, MINB) void attn_bwd_kv_kernel(const pico_attn_args a, float scale, float scale_log2,
                                                               const float* __restrict__ lse2_g,
                                                               const float* __restrict__ delta_g, int sq_pad,
                                                               int hsplit, float* __restrict__ dkv_part,
                                                               unsigned long long* __restrict__ stamp_out,
-                                                              const BlkGroups grp) {
+                                                              const BlkGroups grp, const int* __restrict__ doc) {
   using C = KVCfg<D>;
+  static_assert(!DOC || CAUSAL, "the document mask is a causal mask");
   constexpr int KS = C::KS, DT = C::DT, CPR = C::CPR, RB = C::RB;
   __shared__ __attribute__((aligned(16))) char smem[C::NBUF * C::SLOT];
 
@@ -77,7 +83,17 @@ __global__ __launch_bounds__(KNW * 64, MINB) void attn_bwd_kv_kernel(const pico_
   const int kw = k0 + KPW * wave;  // this wave's first key
 
   const int qstart = CAUSAL ? k0 : 0;  // k0 is a multiple of QT
-  const int nqt = Sq > qstart ? (Sq - qstart + QT - 1) / QT : 0;
+  // the last query row + 1 that any key of the block sees; DOC: the end of the block's last valid key, this
+  // wave's first key's end (the least of the wave) and this lane's key's end
+  int qlim = Sq, end_first = Sq, end_lane = Sq;
+  if constexpr (DOC) {
+    const int* de = doc + ((int64_t)a.batch + b) * Sq;
+    const int last = min(k0 + KVB, Sk) - 1, key = kw + r;  // k0 < Sk for every workgroup
+    qlim = __builtin_amdgcn_readfirstlane(min(max(de[last], last + 1), Sq));
+    end_lane = min(max(de[min(key, Sk - 1)], key + 1), Sq);
+    end_first = __builtin_amdgcn_readlane(end_lane, 0);
+  }
+  const int nqt = qlim > qstart ? (qlim - qstart + QT - 1) / QT : 0;
   const int ntot = G * nqt;
   const int tb = (int)((int64_t)ntot * hs / hsplit);
   const int ntiles = (int)((int64_t)ntot * (hs + 1) / hsplit) - tb;
@@ -160,8 +176,11 @@ __global__ __launch_bounds__(KNW * 64, MINB) void attn_bwd_kv_kernel(const pico_
         static_assert(C::NP % KNW == 1 && C::NP / KNW == C::NPW - 1, "the LSE / delta piece is wave 0's last");
         // (from an opaque copy of the lane id: a plain __lane_id() expression is loop-invariant and gets hoisted
         // out of the tile loop into that same long-lived, spilled VGPR)
+        // (DOC, with the lane's end live as well: even that copy's source was spilled at D = 64 and reloaded here
+        // every tile, so the lane id is counted afresh)
         int l = lane0;
-        asm volatile("" : "+v"(l));
+        if constexpr (DOC) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        else asm volatile("" : "+v"(l));
         l &= 15;
         dma_piece(c.p[i], (unsigned)(16 * (l & 7)) + ((l >> 3) ? delta_off : 0u), dst + pc_dst[i]);
       }
@@ -248,15 +267,21 @@ __global__ __launch_bounds__(KNW * 64, MINB) void attn_bwd_kv_kernel(const pico_
     }
     // The causal / padding mask enters as the C operand of each S chain's first MFMA (-inf where key > q or
     // key >= Sk, else 0): the branch covers only those MFMAs, the rest of the tile is straight-line code.
-    if ((CAUSAL && kw + KPW - 1 > q0) || kpad) {  // wave-uniform: diagonal / wholly masked tiles, padding keys
+    // (DOC: also the tiles whose last row reaches the end of the wave's first key)
+    if ((CAUSAL && kw + KPW - 1 > q0) || kpad || (DOC && q0 + QT > end_first)) {  // wave-uniform: diagonal / wholly masked tiles, padding keys
 #pragma unroll
       for (int kt = 0; kt < KH; ++kt) {
         const int key = kw + 32 * kt + r;
         // masked iff (i&3) + 8(i>>2) < rel: causal key > q, or every row for a padding key
         const int rel = key >= Sk ? 64 : (CAUSAL ? key - q0 - 4 * h : -1);
+        const int rel_hi = end_lane - q0 - 4 * h;  // DOC: ... or >= rel_hi: the row is past the key's document
         f32x16 m;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) m[i] = ((i & 3) + 8 * (i >> 2) < rel) ? -INFINITY : 0.f;
+        for (int i = 0; i < 16; ++i) {
+          const int c = (i & 3) + 8 * (i >> 2);
+          if constexpr (DOC) m[i] = (c < rel || c >= rel_hi) ? -INFINITY : 0.f;
+          else m[i] = (c < rel) ? -INFINITY : 0.f;
+        }
         s[kt] = mfma32(qa[0], kf[kt][0], m);
       }
     } else {
@@ -457,13 +482,15 @@ __global__ __launch_bounds__(KNW * 64, MINB) void attn_bwd_kv_kernel(const pico_
 
 }  // namespace
 
-int attn_bwd_kv_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s) {
-  const auto kernel = a->head_dim == 128 ? (a->causal ? attn_bwd_kv_kernel<128, true, kv_minb(128, true)>
+int attn_bwd_kv_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s, const int* doc) {
+  const auto kernel = p.doc ? (a->head_dim == 128 ? attn_bwd_kv_kernel<128, true, kv_minb(128, true), true>
+                                                  : attn_bwd_kv_kernel<64, true, kv_minb(64, true), true>)
+                    : a->head_dim == 128 ? (a->causal ? attn_bwd_kv_kernel<128, true, kv_minb(128, true)>
                                                       : attn_bwd_kv_kernel<128, false, kv_minb(128, false)>)
                                          : (a->causal ? attn_bwd_kv_kernel<64, true, kv_minb(64, true)>
                                                       : attn_bwd_kv_kernel<64, false, kv_minb(64, false)>);
   return pico_launch(PICO_K_ATTN_BWD_KV, "attn_bwd_kv", kernel, dim3((int)p.kv_grid), dim3(KNW * 64), 0, s, *a,
                      a->softmax_scale, a->softmax_scale * LOG2E, split_ws<float>(a, p.lse2_off),
                      split_ws<float>(a, p.delta_off), p.sq_pad, p.hsplit, split_ws<float>(a, p.part_off),
-                     split_ws<unsigned long long>(a, p.stamp_off), p.grp);
+                     split_ws<unsigned long long>(a, p.stamp_off), p.grp, doc);
 }

@@ -35,9 +35,11 @@ struct SplitEnv {
   int cus;                 // compute units of the device
   int kvp, waves, groups;  // PICO_SEL_ATTN_KVP, PICO_SEL_KVP_WAVES, PICO_SEL_ATTN_GROUPS (PICO_SEL_AUTO: the shape rule)
   int64_t stamp_bytes;     // workspace tail of a diagnostic stamp build (attn_bwd_split.h STAMP_BYTES), else 0
+  int doc;                 // 1: a document-masked call (pico_attn_doc_bwd), see split_plan; else 0
 };
 
 struct SplitPlan {
+  bool doc;    // the DOC instantiations of the dQ and the 32-row dK/dV kernel (SplitEnv::doc)
   bool kvp;    // dK/dV by the 64-row kernel (attn_bwd_kvp_kernel at D = 64, attn_bwd_kvp128_kernel at 128), else the 32-row one
   int waves;   // waves (x 32 keys) per dK/dV workgroup: 4, or 8 (attn_bwd_kvp_kernel only)
   int kvb;     // keys per dK/dV workgroup block = 32 waves
@@ -162,14 +164,20 @@ inline BlkGroups kv_groups(const pico_attn_args* a, const SplitPlan& p, const Sp
   return block_groups(wt, nkb, a->batch * a->heads_kv, p.minb, e.cus);
 }
 
+// e.doc (a document-masked causal call): only the 32-row dK/dV kernel has a masked form, so it runs for both head
+// dims whatever PICO_SEL_ATTN_KVP says, and the one-round block groups are off (their weights count the query tiles
+// of the plain causal mask; under the document mask a key block's list ends with its last key's document, which
+// the host does not know). hsplit is still sized from the shape alone; a share that the shortened list leaves
+// empty writes zero partials. With e.doc == 0 every result is what it was.
 inline SplitPlan split_plan(const pico_attn_args* a, const SplitEnv& e) {
   SplitPlan p{};
-  p.kvp = kvp_enabled(a, e.kvp);
+  p.doc = e.doc != 0;
+  p.kvp = !p.doc && kvp_enabled(a, e.kvp);
   p.waves = p.kvp && a->head_dim == 64 ? kvp_waves(a, e.waves) : KVB / 32;
   p.kvb = 32 * p.waves;
   p.minb = p.kvp && a->head_dim == 64 ? kvp_minb(p.waves) : kv_minb((int)a->head_dim, a->causal != 0);
   p.hsplit = kv_hsplit(a, p.kvb, p.minb);
-  p.grp = kv_groups(a, p, e);
+  p.grp = p.doc ? BlkGroups{} : kv_groups(a, p, e);
   p.q_front = q_front(a, e.cus);
   p.sq_pad = (int)((a->seqlen_q + 63) / 64) * 64;
   p.q_grid = (a->seqlen_q + QB - 1) / QB * a->batch * a->heads_q;

@@ -35,12 +35,19 @@ struct QCfg {
 
 // (Round 5 measured and removed a pipelined form of this tile — the two 32-key halves as one hand-ordered stream
 // of 24 MFMA slots at two workgroups per CU, as attn_bwd_kvp_kernel: C2 40.5 vs 40.6 us, profiles/r05_ab_kvp_qp.jsonl.)
-template <int D, bool CAUSAL>
+// DOC (pico_attn_doc_bwd): `doc` is the start plane of the document bounds, int32 [B][Sq]; the rules are the
+// forward's (attn_fwd_kernel): per-lane start clamped into [0, my_q], the sweep begins at the tile of the
+// workgroup's first row's start (workgroup-uniform, in an SGPR), a wave skips the tiles wholly before its first
+// row's start and masks every tile that begins before its last row's start. The ring is indexed relative to the
+// first tile (slot = (tile - first) % NBUF), so no rounding is needed here.
+template <int D, bool CAUSAL, bool DOC = false>
 __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pico_attn_args a, float scale, float scale_log2,
                                                              float* __restrict__ lse2_g, float* __restrict__ delta_g,
                                                              int sq_pad, unsigned long long* __restrict__ stamp_out,
-                                                             int nfront, float lse_mul, float lse_pad) {
+                                                             int nfront, float lse_mul, float lse_pad,
+                                                             const int* __restrict__ doc) {
   using C = QCfg<D>;
+  static_assert(!DOC || CAUSAL, "the document mask is a causal mask");
 #if PICO_BWDQ_WGSTAMP
   unsigned long long wgs[4];
   wgs[0] = __builtin_amdgcn_s_memrealtime();
@@ -79,6 +86,15 @@ __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pi
   const int lim_last = CAUSAL ? min(qw + 31, Sk - 1) : Sk - 1;   // last key any row of the wave sees
   const int lim_first = CAUSAL ? min(qw, Sk - 1) : Sk - 1;       // keys <= this need no mask
   const int lim_lane = CAUSAL ? min(my_q, Sk - 1) : Sk - 1;      // this lane's row sees keys <= it
+  // DOC: this lane's row sees keys >= lo_lane; the wave's first / last row's start; the workgroup's first tile
+  int lo_lane = 0, lo_first = 0, lo_last = 0, tbeg = 0;
+  if constexpr (DOC) {
+    const int* ds = doc + (int64_t)b * Sq;
+    lo_lane = max(0, min(ds[qc], my_q));
+    lo_first = __builtin_amdgcn_readlane(lo_lane, 0);
+    lo_last = __builtin_amdgcn_readlane(lo_lane, 31);
+    tbeg = __builtin_amdgcn_readfirstlane(max(0, min(ds[q0], q0))) / KT;  // q0 < Sq for every workgroup
+  }
 
   // ---- DMA: piece j = wave + 4 i of a tile; j < NP/2: K image piece j, else V image piece j - NP/2 ----
   int src_row[C::NPW], src_col[C::NPW];
@@ -100,16 +116,29 @@ __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pi
   for (int i = 0; i < C::NPW; ++i) full_off[i] = (unsigned)(src_row[i] * (is_k[i] ? ksd : vsd) + src_col[i]) * 2u;
   // K and V tile rows advance by constant byte strides: wave-uniform pointers, bumped per tile
   const int64_t kst = (int64_t)KT * ksd * 2, vst = (int64_t)KT * vsd * 2;
-  const char* kp_nxt = (const char*)kg;
-  const char* vp_nxt = (const char*)vg;
+  const char* kp_nxt = (const char*)kg + tbeg * kst;
+  const char* vp_nxt = (const char*)vg + tbeg * vst;
   auto issue_piece = [&](int tile, int slot_i, int i) __attribute__((always_inline)) {
     const unsigned slot = smem_lds + (unsigned)slot_i * (unsigned)C::SLOT;
     const int base = tile * KT;
     const int lastrow = Sk - 1 - base;  // rows past it are clamped (finite; masked by the softmax)
     const bool full = base + KT <= Sk;
     const char* tb = is_k[i] ? kp_nxt : vp_nxt;
-    const unsigned off = full ? full_off[i]
-                              : (unsigned)(min(src_row[i], lastrow) * (is_k[i] ? ksd : vsd) + src_col[i]) * 2u;
+    unsigned off;
+    if constexpr (!DOC) {
+      off = full ? full_off[i] : (unsigned)(min(src_row[i], lastrow) * (is_k[i] ? ksd : vsd) + src_col[i]) * 2u;
+    } else {
+      off = full_off[i];
+      if (!full) {
+        // the partial last tile re-derives its row and column from the lane id: held for the whole sweep beside
+        // the lane's start they cost the D = 64 kernel a spilled dword, reloaded here inside the tile loop
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int j = wave + 4 * i;
+        const int row = C::RPP * (is_k[i] ? j : j - C::NP / 2) + ln / C::CPR;
+        off = (unsigned)(min(row, lastrow) * (is_k[i] ? ksd : vsd) + 8 * ((ln % C::CPR) ^ swz<D>(row))) * 2u;
+      }
+    }
     dma_piece(tb, off, slot + dst_off[i]);
   };
   auto bump = [&]() __attribute__((always_inline)) {
@@ -124,7 +153,7 @@ __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pi
   constexpr int P = C::NBUF - 1;  // prefetch distance
 #pragma unroll
   for (int t = 0; t < P; ++t)
-    if (t < ntiles) issue(t, t);
+    if (tbeg + t < ntiles) issue(tbeg + t, t);
 
   // ---- Q, dO fragments (B operands), delta = rowsum(dO * O), LSE ----
   bf16x8 qf[KS], df[KS];
@@ -195,9 +224,14 @@ __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pi
       f32x16 sc, dpc;
       if (mask) {
         const int rel = lim_lane - n0 - 4 * h;
+        const int rel_lo = lo_lane - n0 - 4 * h;  // DOC: key allowed iff rel_lo <= c <= rel
         f32x16 m;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) m[i] = (32 * kt + (i & 3) + 8 * (i >> 2)) <= rel ? 0.f : -INFINITY;
+        for (int i = 0; i < 16; ++i) {
+          const int c = 32 * kt + (i & 3) + 8 * (i >> 2);
+          if constexpr (DOC) m[i] = c <= rel && c >= rel_lo ? 0.f : -INFINITY;
+          else m[i] = c <= rel ? 0.f : -INFINITY;
+        }
         sc = mfma32(kf[0], qf[0], m);
       } else {
         sc = mfma32(kf[0], qf[0], (f32x16)0.f);
@@ -230,12 +264,12 @@ __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pi
   __builtin_amdgcn_s_waitcnt(0xC07F);
 #endif
   // unrolled by the ring depth: every LDS read of a tile has a compile-time slot (immediate offsets)
-  for (int t0 = 0; t0 < ntiles; t0 += C::NBUF) {
+  for (int t0 = tbeg; t0 < ntiles; t0 += C::NBUF) {  // tile t sits in slot (t - tbeg) % NBUF = u
 #pragma unroll
     for (int u = 0; u < C::NBUF; ++u) {
       const int t = t0 + u;
       if (t >= ntiles) break;
-      if (t > 0) {  // tile t landed (this wave's pieces); the younger tiles stay in flight
+      if (t > tbeg) {  // tile t landed (this wave's pieces); the younger tiles stay in flight
         if constexpr (P == 2) {  // counts as immediates (a runtime wait_vmcnt(n) is a compare-and-branch chain)
           if (t + 1 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NPW) : "memory");
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -247,9 +281,10 @@ __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pi
       }
       lds_barrier();  // every wave's pieces of tile t visible; slot (t + P) % NBUF no longer read
       const int n0 = t * KT;
-      const bool busy = n0 <= lim_last;  // wave-uniform: some row of the wave sees some key of the tile
+      // wave-uniform: some row of the wave sees some key of the tile
+      const bool busy = n0 <= lim_last && (!DOC || n0 + KT > lo_first);
       if (t + P < ntiles) issue(t + P, (u + P) % C::NBUF);
-      if (busy) tile(smem + u * C::SLOT, n0 + KT - 1 > lim_first, n0);
+      if (busy) tile(smem + u * C::SLOT, n0 + KT - 1 > lim_first || (DOC && n0 < lo_last), n0);
     }
   }
 
@@ -304,12 +339,14 @@ __global__ __launch_bounds__(256, QCfg<D>::MINB) void attn_bwd_q_kernel(const pi
 
 }  // namespace
 
-int attn_bwd_q_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s) {
-  const auto kernel = a->head_dim == 64 ? (a->causal ? attn_bwd_q_kernel<64, true> : attn_bwd_q_kernel<64, false>)
-                                        : (a->causal ? attn_bwd_q_kernel<128, true> : attn_bwd_q_kernel<128, false>);
+int attn_bwd_q_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s, const int* doc) {
+  const auto kernel =
+      p.doc ? (a->head_dim == 64 ? attn_bwd_q_kernel<64, true, true> : attn_bwd_q_kernel<128, true, true>)
+            : a->head_dim == 64 ? (a->causal ? attn_bwd_q_kernel<64, true> : attn_bwd_q_kernel<64, false>)
+                                : (a->causal ? attn_bwd_q_kernel<128, true> : attn_bwd_q_kernel<128, false>);
   // the LSE form the dK/dV kernel reads: LSE log2 e (+inf padding rows) for the 32-row one, -LSE / scale (-inf) for the 64-row ones
   return pico_launch(PICO_K_ATTN_BWD_Q, "attn_bwd_q", kernel, dim3((int)p.q_grid), dim3(256), 0, s, *a,
                      a->softmax_scale, a->softmax_scale * LOG2E, split_ws<float>(a, p.lse2_off),
                      split_ws<float>(a, p.delta_off), p.sq_pad, split_ws<unsigned long long>(a, p.stamp_off), p.q_front,
-                     p.kvp ? -1.0f / a->softmax_scale : LOG2E, p.kvp ? -INFINITY : INFINITY);
+                     p.kvp ? -1.0f / a->softmax_scale : LOG2E, p.kvp ? -INFINITY : INFINITY, doc);
 }

@@ -90,8 +90,9 @@ PICO_DEV void acc_drain4(f32x16 (&v)[4]) {
 }
 
 // The launchers, one per kernel file: the pico_launch of the instantiation the shape and the plan name.
-int attn_bwd_q_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s);       // attn_bwd_q.hip
-int attn_bwd_kv_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s);      // attn_bwd_kv.hip
+// doc: the document bounds of a masked call (int32 [2][B][S], start plane then end plane; p.doc), else null.
+int attn_bwd_q_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s, const int* doc);   // attn_bwd_q.hip
+int attn_bwd_kv_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s, const int* doc);  // attn_bwd_kv.hip
 int attn_bwd_kvp_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s);     // attn_bwd_kvp.hip, D = 64
 int attn_bwd_kvp128_launch(const pico_attn_args* a, const SplitPlan& p, hipStream_t s);  // attn_bwd_kvp128.hip
 

@@ -61,21 +61,22 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const pico_attn_args 
   }
 }
 
-SplitPlan plan_of(const pico_attn_args* a) {
+SplitPlan plan_of(const pico_attn_args* a, bool doc) {
   return split_plan(a, SplitEnv{pico_num_cus(), pico_sel(PICO_SEL_ATTN_KVP), pico_sel(PICO_SEL_KVP_WAVES),
-                                pico_sel(PICO_SEL_ATTN_GROUPS), STAMP_BYTES});
+                                pico_sel(PICO_SEL_ATTN_GROUPS), STAMP_BYTES, doc ? 1 : 0});
 }
 
 }  // namespace
 
-int64_t pico_attn_bwd_split_workspace(const pico_attn_args* a) { return plan_of(a).bytes; }
+// doc (workspace query: whether; launch: the bounds, int32 [2][B][S], or null): the document-masked call
+int64_t pico_attn_bwd_split_workspace(const pico_attn_args* a, bool doc) { return plan_of(a, doc).bytes; }
 
-int pico_attn_bwd_split(const pico_attn_args* a, hipStream_t s) {
-  const SplitPlan p = plan_of(a);
+int pico_attn_bwd_split(const pico_attn_args* a, hipStream_t s, const int* doc) {
+  const SplitPlan p = plan_of(a, doc != nullptr);
   PICO_REQUIRE(p.q_grid < (1ll << 31), "pico_attn_bwd: grid too large");
-  PICO_TRY(attn_bwd_q_launch(a, p, s));
+  PICO_TRY(attn_bwd_q_launch(a, p, s, doc));
   if (p.kv_grid == 0) return 0;
-  PICO_TRY(!p.kvp ? attn_bwd_kv_launch(a, p, s)
+  PICO_TRY(!p.kvp ? attn_bwd_kv_launch(a, p, s, doc)
                   : a->head_dim == 64 ? attn_bwd_kvp_launch(a, p, s) : attn_bwd_kvp128_launch(a, p, s));
   if (p.hsplit > 1) {
     const int blocks = pico_cdiv(a->batch * a->seqlen_k * a->heads_kv * (a->head_dim / 16), 256);

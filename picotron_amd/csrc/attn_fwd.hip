@@ -104,10 +104,18 @@ PICO_DEV float halves_sum(float x) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-template <int D, bool CAUSAL>
+// DOC (causal self-attention of packed rows, pico_attn_doc_fwd): `doc` is the start plane of the document bounds,
+// int32 [B][Sq]; query i of row b sees key j iff doc[b][i] <= j <= i. Each lane clamps its row's start into
+// [0, my_q] (a bad bound costs numbers, never an address). Tiles wholly before the start of the workgroup's first
+// row are never loaded: the sweep begins at that tile, rounded down to the ring depth (a tile's slot is tile % NBUF),
+// a workgroup-uniform value held in an SGPR, so that every wave takes every barrier and the LDS-DMA destination can
+// go through m0. A wave skips the tiles wholly before its first row's start and runs the masked body on every tile
+// that begins before its last row's start. Everything DOC adds sits under `if constexpr (DOC)`.
+template <int D, bool CAUSAL, bool DOC = false>
 __global__ __launch_bounds__(256, FwdCfg<D>::WAVES_PER_EU)
-__attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER_EU))) void attn_fwd_kernel(const pico_attn_args a, float scale_log2, int round_len) {
+__attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER_EU))) void attn_fwd_kernel(const pico_attn_args a, float scale_log2, int round_len, const int* __restrict__ doc) {
   using C = FwdCfg<D>;
+  static_assert(!DOC || CAUSAL, "the document mask is a causal mask");
   constexpr bool EARLY_V = PICO_FWD_EARLY_V < 0 ? D == 128 : PICO_FWD_EARLY_V != 0;
   constexpr int KS = C::KS;  // k-steps of the S^T product
   constexpr int DT = C::DT;  // 32-wide output tiles of O^T
@@ -180,6 +188,16 @@ __attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER
   const int lim_last = CAUSAL ? min(qw + 31, Sk - 1) : Sk - 1;
   const int lim_first = CAUSAL ? min(qw, Sk - 1) : Sk - 1;
   const int lim_lane = CAUSAL ? min(my_q, Sk - 1) : Sk - 1;  // this lane's row: keys <= lim_lane
+  // DOC: this lane's row sees keys >= lo_lane; the wave's first / last row's start; the workgroup's first tile
+  int lo_lane = 0, lo_first = 0, lo_last = 0, tbeg = 0;
+  if constexpr (DOC) {
+    const int* ds = doc + (int64_t)b * Sq;
+    lo_lane = max(0, min(ds[min(my_q, Sq - 1)], my_q));
+    lo_first = __builtin_amdgcn_readlane(lo_lane, 0);
+    lo_last = __builtin_amdgcn_readlane(lo_lane, 31);
+    const int wg_lo = __builtin_amdgcn_readfirstlane(max(0, min(ds[q0], q0)));  // q0 < Sq for every workgroup
+    tbeg = wg_lo / BN / C::NBUF * C::NBUF;
+  }
 
   // ---- LDS-DMA staging: piece j (wave w issues j = w, w + 4, ...) ----
   // K piece (j < 2 KS): image ks = j / 2, rows 32 (j & 1) + lane / 2, LDS chunk lane & 1, which holds
@@ -300,12 +318,14 @@ __attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER
     // lane holds row my_q, keys n0 + 32 kt + acc_row(i, h) = n0 + 4h + c(kt, i)
     if (mask) {  // wave-uniform
       const int rel = lim_lane - n0 - 4 * h;  // key allowed iff c <= rel
+      const int rel_lo = lo_lane - n0 - 4 * h;  // DOC: ... and c >= rel_lo
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int c = 32 * kt + (i & 3) + 8 * (i >> 2);
-          s[kt][i] = c <= rel ? s[kt][i] : -INFINITY;
+          if constexpr (DOC) s[kt][i] = c <= rel && c >= rel_lo ? s[kt][i] : -INFINITY;
+          else s[kt][i] = c <= rel ? s[kt][i] : -INFINITY;
         }
     }
   };
@@ -364,7 +384,7 @@ __attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER
   constexpr int P = C::NBUF - 1;  // prefetch distance
 #pragma unroll
   for (int t = 0; t < P; ++t)
-    if (t < ntiles) issue(t);
+    if (tbeg + t < ntiles) issue(tbeg + t);
   if (rope_q) {
 #pragma unroll
     for (int ks = 0; ks < KS / 2; ++ks) {
@@ -389,7 +409,7 @@ __attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER
   __builtin_amdgcn_s_waitcnt(0xC07F);
 #endif
   // unrolled by the ring depth: every ring slot is a compile-time offset in the LDS reads
-  for (int t0 = 0; t0 < ntiles; t0 += C::NBUF) {
+  for (int t0 = tbeg; t0 < ntiles; t0 += C::NBUF) {  // tbeg is a multiple of NBUF: tile t sits in slot u
 #pragma unroll
     for (int u = 0; u < C::NBUF; ++u) {
       const int t = t0 + u;
@@ -406,10 +426,10 @@ __attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER
       if (t + P < ntiles) issue(t + P);
       const int n0 = t * BN;
       // wave-uniform: skip (tile above every row), full (every key visible to every row), or masked
-      if (n0 <= lim_last) {
+      if (n0 <= lim_last && (!DOC || n0 + BN > lo_first)) {
         const unsigned slot = (unsigned)u * (unsigned)C::SLOT;
         const char* kb = smem + (slot + k_lane);
-        tile_body(kb, smem_lds + slot + v_lane, n0, n0 + BN - 1 > lim_first);
+        tile_body(kb, smem_lds + slot + v_lane, n0, n0 + BN - 1 > lim_first || (DOC && n0 < lo_last));
       }
     }
   }
@@ -475,17 +495,19 @@ __attribute__((amdgpu_waves_per_eu(FwdCfg<D>::WAVES_PER_EU, FwdCfg<D>::WAVES_PER
 }
 
 template <int D>
-int launch_fwd(const pico_attn_args* a, hipStream_t s) {
+int launch_fwd(const pico_attn_args* a, hipStream_t s, const int* doc = nullptr) {
   const int nmb = (int)((a->seqlen_q + BM - 1) / BM);
   const int64_t nblk = (int64_t)nmb * a->batch * a->heads_q;
   PICO_REQUIRE(nblk < (1ll << 31), "pico_attn_fwd: grid too large");
   const float sl2 = a->softmax_scale * LOG2E;
   PICO_REQUIRE(sl2 > 0.f, "pico_attn_fwd: softmax_scale must be positive");
   const int rl = pico_num_cus() / 8 * 8 > 0 ? pico_num_cus() / 8 * 8 : 8;  // snake rounds: whole XCD groups
-  if (a->causal) {
-    PICO_TRY(pico_launch(PICO_K_ATTN_FWD, "attn_fwd", attn_fwd_kernel<D, true>, dim3((int)nblk), dim3(256), 0, s, *a, sl2, rl));
+  if (doc) {
+    PICO_TRY(pico_launch(PICO_K_ATTN_FWD, "attn_doc_fwd", attn_fwd_kernel<D, true, true>, dim3((int)nblk), dim3(256), 0, s, *a, sl2, rl, doc));
+  } else if (a->causal) {
+    PICO_TRY(pico_launch(PICO_K_ATTN_FWD, "attn_fwd", attn_fwd_kernel<D, true>, dim3((int)nblk), dim3(256), 0, s, *a, sl2, rl, doc));
   } else {
-    PICO_TRY(pico_launch(PICO_K_ATTN_FWD, "attn_fwd", attn_fwd_kernel<D, false>, dim3((int)nblk), dim3(256), 0, s, *a, sl2, rl));
+    PICO_TRY(pico_launch(PICO_K_ATTN_FWD, "attn_fwd", attn_fwd_kernel<D, false>, dim3((int)nblk), dim3(256), 0, s, *a, sl2, rl, doc));
   }
   return 0;
 }
@@ -493,25 +515,42 @@ int launch_fwd(const pico_attn_args* a, hipStream_t s) {
 }  // namespace
 
 int pico_attn_check_common(const pico_attn_args* a, const char* op);
+int pico_attn_check_doc(const pico_attn_args* a, const void* doc_bounds, const char* op);
 int pico_attn_fwdp(const pico_attn_args* a, hipStream_t s);
-extern "C" int pico_attn_fwd(const pico_attn_args* a, void* stream) {
-  int rc = pico_attn_check_common(a, "pico_attn_fwd");
-  if (rc) return rc;
-  PICO_REQUIRE(a->o && a->lse, "pico_attn_fwd: null output");
-  PICO_REQUIRE(!a->o_t || a->o_t_ld >= a->batch * a->seqlen_q, "pico_attn_fwd: o_t_ld must cover the tokens");
+
+// the checks of pico_attn_fwd (op names the entry point in the messages); doc = the start plane, or null
+static int attn_fwd_entry(const pico_attn_args* a, const int* doc, void* stream, const char* op) {
+  PICO_REQUIRE(a->o && a->lse, "%s: null output", op);
+  PICO_REQUIRE(!a->o_t || a->o_t_ld >= a->batch * a->seqlen_q, "%s: o_t_ld must cover the tokens", op);
   if (a->flags & PICO_ATTN_ROPE_Q_FWD) {
-    PICO_REQUIRE(a->dq && a->rope_cos && a->rope_sin, "pico_attn_fwd: ROPE_Q_FWD needs dq and the cos/sin tables");
+    PICO_REQUIRE(a->dq && a->rope_cos && a->rope_sin, "%s: ROPE_Q_FWD needs dq and the cos/sin tables", op);
     PICO_REQUIRE(((uintptr_t)a->dq | (uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin) % 16 == 0,
-                 "pico_attn_fwd: ROPE_Q_FWD needs 16-byte aligned dq and tables");
+                 "%s: ROPE_Q_FWD needs 16-byte aligned dq and tables", op);
     PICO_REQUIRE(a->rope_stride % 8 == 0 && a->rope_stride >= a->head_dim / 2,
-                 "pico_attn_fwd: bad rope table row stride %lld", (long long)a->rope_stride);
+                 "%s: bad rope table row stride %lld", op, (long long)a->rope_stride);
     for (int d = 0; d < 3; ++d)
-      PICO_REQUIRE(a->dq_strides[d] % 8 == 0, "pico_attn_fwd: dq strides must be multiples of 8 elements");
+      PICO_REQUIRE(a->dq_strides[d] % 8 == 0, "%s: dq strides must be multiples of 8 elements", op);
   }
   if (a->batch == 0 || a->seqlen_q == 0 || a->heads_q == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const int rp = pico_attn_fwdp(a, s);  // the persistent 64-row-per-wave kernel where it applies (attn_fwdp.hip)
-  if (rp >= 0) return rp;
-  if (a->head_dim == 64) return launch_fwd<64>(a, s);
-  return launch_fwd<128>(a, s);
+  if (!doc) {
+    const int rp = pico_attn_fwdp(a, s);  // the persistent 64-row-per-wave kernel where it applies (attn_fwdp.hip)
+    if (rp >= 0) return rp;
+  }
+  if (a->head_dim == 64) return launch_fwd<64>(a, s, doc);
+  return launch_fwd<128>(a, s, doc);
+}
+
+extern "C" int pico_attn_fwd(const pico_attn_args* a, void* stream) {
+  int rc = pico_attn_check_common(a, "pico_attn_fwd");
+  if (rc) return rc;
+  return attn_fwd_entry(a, nullptr, stream, "pico_attn_fwd");
+}
+
+// Document-masked causal forward of packed rows: doc_bounds = ops.doc_bounds, int32 [2][B][S] (this kernel reads
+// plane 0, the starts). The persistent forward (PICO_SEL_ATTN_FWD) has no masked form and is not consulted.
+extern "C" int pico_attn_doc_fwd(const pico_attn_args* a, const void* doc_bounds, void* stream) {
+  int rc = pico_attn_check_doc(a, doc_bounds, "pico_attn_doc_fwd");
+  if (rc) return rc;
+  return attn_fwd_entry(a, (const int*)doc_bounds, stream, "pico_attn_doc_fwd");
 }

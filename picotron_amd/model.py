@@ -69,6 +69,13 @@ def require_kernel_path():
                            "FLASH_ATTEN=0 path is not provided); unset FLASH_ATTEN or set it to 1")
 
 
+def _refuse_doc_mask_under_cp():
+    """The ring attention of context parallelism has no document-masked form: a doc_start is refused there."""
+    if os.getenv("CONTEXT_PARALLEL", "0") == "1" or pgm.cp_rank_and_size()[1] > 1:
+        raise NotImplementedError("document-masked attention (doc_start / doc_bounds) is not available under "
+                                  "context parallelism: the ring attention path has no masked kernels")
+
+
 def _table_device():
     if os.getenv("DEVICE", "cuda") == "cuda" and torch.cuda.is_available():
         return torch.device("cuda", torch.cuda.current_device())
@@ -189,7 +196,8 @@ class Attention(nn.Module):
             return None
         return _col_parallel((self.q_proj, self.k_proj, self.v_proj))
 
-    def forward(self, x, cos, sin, attention_mask=None, position_ids=None, out_hint=None):
+    def forward(self, x, cos, sin, attention_mask=None, position_ids=None, out_hint=None, doc_bounds=None):
+        """doc_bounds (ops.doc_bounds of the micro-batch, or None): the document mask of packed rows."""
         require_kernel_path()
         B, S, _ = x.size()
         D = self.head_dim
@@ -199,7 +207,8 @@ class Attention(nn.Module):
             # under TP the local shards, with one f region (input-gradient all-reduce) for all three
             x = _tp_input(kind, x)
             out = ops.qkv_rope_attention(x, self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, cos, sin,
-                                         self.num_local_heads, self.num_local_kv_heads, True, out_hint=out_hint)
+                                         self.num_local_heads, self.num_local_kv_heads, True, out_hint=out_hint,
+                                         doc_bounds=doc_bounds)
             return _proj(self.out_proj, out)
         q = self.q_proj(x).view(B, S, self.num_local_heads, D)
         k = self.k_proj(x).view(B, S, self.num_local_kv_heads, D)
@@ -207,7 +216,10 @@ class Attention(nn.Module):
         q = ops.apply_rotary_emb(q, cos[:, : D // 2], sin[:, : D // 2])
         k = ops.apply_rotary_emb(k, cos[:, : D // 2], sin[:, : D // 2])
         causal = q.size(1) == k.size(1)
-        if os.getenv("CONTEXT_PARALLEL", "0") == "1":
+        if doc_bounds is not None:
+            _refuse_doc_mask_under_cp()
+            out = ops.flash_attn_doc_func(q, k, v, doc_bounds)
+        elif os.getenv("CONTEXT_PARALLEL", "0") == "1":
             # the reference's call: [B, H, S, D] in, [B, H, S, D] out, transposed back (ref :139-150)
             from .context_parallel import context_parallel
             out = context_parallel.ring_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
@@ -268,9 +280,9 @@ class DecoderLayer(nn.Module):
         from .context_parallel.context_parallel import update_rope_for_context_parallel
         self.cos, self.sin = update_rope_for_context_parallel(cos, sin)
 
-    def forward(self, x, attention_mask=None, position_ids=None):
+    def forward(self, x, attention_mask=None, position_ids=None, doc_bounds=None):
         cos, sin = self.cos, self.sin
-        x = x + self.attention(self.input_layernorm(x), cos, sin, attention_mask, position_ids)
+        x = x + self.attention(self.input_layernorm(x), cos, sin, attention_mask, position_ids, doc_bounds=doc_bounds)
         x = x + self.mlp(self.post_attention_layernorm(x))
         return x
 
@@ -287,7 +299,7 @@ class DecoderLayer(nn.Module):
         return {"qkv": Proj.of(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight), "out": Proj.of(a.out_proj.weight),
                 "gu": Proj.of(m.gate_proj.weight, m.up_proj.weight), "down": Proj.of(m.down_proj.weight)}
 
-    def forward_fused(self, delta, residual, prev_down=None, hints=None):
+    def forward_fused(self, delta, residual, prev_down=None, hints=None, doc_bounds=None):
         """Same layer with the residual adds fused into the norms (layer_norm_fn prenorm form):
         the layer input is residual + delta (residual None for the first layer). Returns the
         (delta, residual) pair whose sum is this layer's output; every sum is rounded to bf16 exactly
@@ -299,7 +311,8 @@ class DecoderLayer(nn.Module):
         # (first layer: the prenorm form without a residual, x is the norm's second output, so the embedding output
         # has one consumer and its gradient needs no separate add)
         h_in, x = self.input_layernorm(delta, residual=residual, prenorm=True, _pair=p_in)
-        attn = self.attention(h_in, self.cos, self.sin, out_hint=hints["out"] if hints else None)
+        attn = self.attention(h_in, self.cos, self.sin, out_hint=hints["out"] if hints else None,
+                              doc_bounds=doc_bounds)
         h2, x = self.post_attention_layernorm(attn, residual=x, prenorm=True, _pair=p_post)
         return self.mlp(h2, down_hint=hints["down"] if hints else None), x
 
@@ -358,19 +371,28 @@ class Llama(nn.Module):
         # NB: the reference never re-initialises final_proj here (ref :262 lacks the call); it is
         # zero-initialised by init_model_with_materialized_weights (ref picotron/checkpoint.py:88-91).
 
-    def forward(self, input_ids, attention_mask=None, position_ids: torch.Tensor = None, return_hidden=False):
+    def forward(self, input_ids, attention_mask=None, position_ids: torch.Tensor = None, return_hidden=False,
+                doc_start=None):
         """Logits [B, S, V] (ref :264-271); return_hidden=True stops after the final norm (the fused LM
-        head + cross-entropy of train._micro_batch consumes it)."""
+        head + cross-entropy of train._micro_batch consumes it). doc_start (int [B, S], ops.doc_starts_from_eos /
+        _from_lengths): packed rows, every layer's attention masked at the document boundaries (token i sees
+        doc_start[b, i] .. i; RoPE positions stay the sequence index); its bounds are computed once here."""
+        doc_bounds = None
+        if doc_start is not None:
+            _refuse_doc_mask_under_cp()
+            if tuple(doc_start.shape) != tuple(input_ids.shape):
+                raise ValueError("Llama.forward: doc_start must have the shape of input_ids")
+            doc_bounds = ops.doc_bounds(doc_start.to(input_ids.device))
         x = self.embedding(input_ids)
         if os.getenv("PICO_UNFUSED", "0") == "1":
             for layer in self.decoder_layers:
-                x = layer(x)
+                x = layer(x) if doc_bounds is None else layer(x, doc_bounds=doc_bounds)
             return self.final_proj(self.final_norm(x))
         delta, residual = x, None
         down = None  # the previous layer's down projection (wgrad_operands.Proj)
         for layer in self.decoder_layers:
             hints = layer._pair_hints()
-            delta, residual = layer.forward_fused(delta, residual, prev_down=down, hints=hints)
+            delta, residual = layer.forward_fused(delta, residual, prev_down=down, hints=hints, doc_bounds=doc_bounds)
             down = hints["down"] if hints else None
         # the fused LM head + CE (return_hidden) groups its weight gradient too: the final norm's y^T goes into the
         # head's x^T group slot

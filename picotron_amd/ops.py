@@ -1161,8 +1161,9 @@ def _check_qkv(q, k, v):
 # Packed rows: several documents share one row of the batch. doc_start[b, i] is the index of the first token of the
 # document that holds token i (non-decreasing along the row, doc_start[b, 0] == 0, doc_start[b, i] <= i); under a
 # document mask query i sees key j iff doc_start[b, i] <= j <= i. The helpers below are plain torch and work on any
-# device; they only describe the mask: no attention kernel takes document bounds (_lib.AttnArgs has no field for
-# them), so nothing in this package applies it.
+# device; they describe the mask. It is applied by the document-masked attention kernels, which take doc_bounds as an
+# argument of their own beside _lib.AttnArgs: flash_attn_doc_func, attention_block_fwd / _bwd(doc_bounds=),
+# qkv_rope_attention(doc_bounds=) and Llama.forward(doc_start=) below and in model.py.
 def doc_starts_from_eos(input_ids, eos_token_id):
     """doc_start int32 [B, S] of packed rows: a token that follows an EOS opens a new document, and token 0
     always does (the EOS itself is the last token of its document)."""
@@ -1233,12 +1234,28 @@ def doc_bounds(doc_start):
     return torch.stack((start, end.to(torch.int32))).contiguous()
 
 
-def attention_block_fwd(q, k, v, softmax_scale, causal, o_t=None, rope_q=None):
+def _check_doc_bounds(doc_bounds, q, k, causal, op):
+    """doc_bounds of a document-masked call: int32 [2, B, S] contiguous on q's device, causal, Sq == Sk."""
+    if not causal:
+        raise ValueError(f"{op}: the document mask is causal; causal=False with doc_bounds")
+    if q.shape[1] != k.shape[1]:
+        raise ValueError(f"{op}: the document mask needs Sq == Sk, got {q.shape[1]} and {k.shape[1]}")
+    if (not torch.is_tensor(doc_bounds) or doc_bounds.dtype != torch.int32 or doc_bounds.device != q.device
+            or tuple(doc_bounds.shape) != (2, q.shape[0], q.shape[1]) or not doc_bounds.is_contiguous()):
+        raise ValueError(f"{op}: doc_bounds must be int32 [2, batch, seqlen] contiguous on q's device "
+                         "(ops.doc_bounds(doc_start))")
+
+
+def attention_block_fwd(q, k, v, softmax_scale, causal, o_t=None, rope_q=None, doc_bounds=None):
     """O [B,Sq,Hq,D] bf16 and LSE [B,Hq,Sq] fp32 (natural log) of softmax(scale*QK^T [+causal]) V.
     o_t (optional, bf16 [Hq*D, >= B*Sq] with unit column stride) also receives O transposed.
     rope_q = (cos, sin) ([>= S, D/2] bf16 tables): q is UNROTATED; the kernel applies RoPE to it in
-    registers and writes the rotated queries back into q in place (PICO_ATTN_ROPE_Q_FWD)."""
+    registers and writes the rotated queries back into q in place (PICO_ATTN_ROPE_Q_FWD).
+    doc_bounds (ops.doc_bounds, int32 [2, B, S]): the document mask of packed rows on top of the causal one
+    (pico_attn_doc_fwd); causal must be set and Sq == Sk."""
     _check_qkv(q, k, v)
+    if doc_bounds is not None:
+        _check_doc_bounds(doc_bounds, q, k, causal, "attention_block_fwd")
     if rope_q is not None and (q.stride(-1) != 1 or any(s % 8 for s in q.stride()[:3])):
         raise ValueError("attention_block_fwd: rope_q rotates q in place; q needs unit last stride and "
                          "strides that are multiples of 8")
@@ -1259,14 +1276,34 @@ def attention_block_fwd(q, k, v, softmax_scale, causal, o_t=None, rope_q=None):
         a.flags |= _lib.ATTN_ROPE_Q_FWD
         a.rope_cos, a.rope_sin, a.rope_stride = _lib.ptr(cos), _lib.ptr(sin), cos.stride(0)
         a.dq, a.dq_strides = _lib.ptr(q), _lib.i64x3(q.stride()[:3])
-    _lib.check(_lib.load().pico_attn_fwd(ctypes.byref(a), _lib.stream_of(q)), "pico_attn_fwd")
+    if doc_bounds is not None:
+        _lib.check(_lib.load().pico_attn_doc_fwd(ctypes.byref(a), _lib.ptr(doc_bounds), _lib.stream_of(q)),
+                   "pico_attn_doc_fwd")
+    else:
+        _lib.check(_lib.load().pico_attn_fwd(ctypes.byref(a), _lib.stream_of(q)), "pico_attn_fwd")
     return o, lse
 
 
-def attention_block_bwd(dout, q, k, v, o, lse, softmax_scale, causal, dq_accum=None):
+def _launch_attn_bwd(a, q, doc_bounds):
+    """Workspace and launch of the attention backward described by `a` (plain, or document-masked)."""
+    lib = _lib.load()
+    size = lib.pico_attn_bwd_workspace_bytes if doc_bounds is None else lib.pico_attn_doc_bwd_workspace_bytes
+    ws = torch.empty(size(ctypes.byref(a)), dtype=torch.uint8, device=q.device)
+    a.workspace = _lib.ptr(ws)
+    if doc_bounds is None:
+        _lib.check(lib.pico_attn_bwd(ctypes.byref(a), _lib.stream_of(q)), "pico_attn_bwd")
+    else:
+        _lib.check(lib.pico_attn_doc_bwd(ctypes.byref(a), _lib.ptr(doc_bounds), _lib.stream_of(q)),
+                   "pico_attn_doc_bwd")
+
+
+def attention_block_bwd(dout, q, k, v, o, lse, softmax_scale, causal, dq_accum=None, doc_bounds=None):
     """(dq, dk, dv) of attention given the (possibly global) O and LSE. If dq_accum (fp32
-    [B,Sq,Hq,D]) is given, dq is ADDED into it and returned instead of a bf16 dq."""
+    [B,Sq,Hq,D]) is given, dq is ADDED into it and returned instead of a bf16 dq. doc_bounds: as in
+    attention_block_fwd (pico_attn_doc_bwd)."""
     _check_qkv(q, k, v)
+    if doc_bounds is not None:
+        _check_doc_bounds(doc_bounds, q, k, causal, "attention_block_bwd")
     _need(dout, "dout")
     if dout.stride(-1) != 1 or any(s % 8 for s in dout.stride()[:3]):
         dout = dout.contiguous()
@@ -1286,10 +1323,7 @@ def attention_block_bwd(dout, q, k, v, o, lse, softmax_scale, causal, dq_accum=N
     a.dq_strides = _lib.i64x3(dq.stride()[:3])
     a.dk_strides = _lib.i64x3(dk.stride()[:3])
     a.dv_strides = _lib.i64x3(dv.stride()[:3])
-    lib = _lib.load()
-    ws = torch.empty(lib.pico_attn_bwd_workspace_bytes(ctypes.byref(a)), dtype=torch.uint8, device=q.device)
-    a.workspace = _lib.ptr(ws)
-    _lib.check(lib.pico_attn_bwd(ctypes.byref(a), _lib.stream_of(q)), "pico_attn_bwd")
+    _launch_attn_bwd(a, q, doc_bounds)
     return dq, dk, dv
 
 
@@ -1307,6 +1341,33 @@ class _FlashAttnFn(torch.autograd.Function):
         q, k, v, o, lse = ctx.saved_tensors
         dq, dk, dv = attention_block_bwd(dout, q, k, v, o, lse, ctx.softmax_scale, ctx.causal)
         return dq, dk, dv, None, None
+
+
+class _FlashAttnDocFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, doc_bounds, softmax_scale):
+        o, lse = attention_block_fwd(q, k, v, softmax_scale, True, doc_bounds=doc_bounds)
+        ctx.save_for_backward(q, k, v, o, lse, doc_bounds)
+        ctx.softmax_scale = softmax_scale
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse, doc_bounds = ctx.saved_tensors
+        dq, dk, dv = attention_block_bwd(dout, q, k, v, o, lse, ctx.softmax_scale, True, doc_bounds=doc_bounds)
+        return dq, dk, dv, None, None
+
+
+def flash_attn_doc_func(q, k, v, doc_bounds, softmax_scale=None):
+    """Causal self-attention of packed rows under the document mask: q [B,S,Hq,D], k/v [B,S,Hkv,D] (HIP bf16, as
+    flash_attn_func) -> out [B,S,Hq,D]; query i of row b sees key j iff doc_start[b, i] <= j <= i.
+    doc_bounds = ops.doc_bounds(doc_start): int32 [2, B, S] contiguous on q's device."""
+    if q.dim() != 4 or k.dim() != 4:
+        raise ValueError("flash_attn_doc_func: q and k must be [batch, seqlen, heads, head_dim]")
+    _check_doc_bounds(doc_bounds, q, k, True, "flash_attn_doc_func")
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
+    return _FlashAttnDocFn.apply(q, k, v, doc_bounds, float(softmax_scale))
 
 
 def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
@@ -1331,8 +1392,9 @@ class _QKVRopeAttentionFn(torch.autograd.Function):
     dW = dqkv^T x (one GEMM, rows = dWq | dWk | dWv)."""
 
     @staticmethod
-    def forward(ctx, x, wq, wk, wv, cos, sin, nh, nkv, causal, out_hint=None):
-        """out_hint: the out-projection reading O (wgrad_operands.Proj: O^T into its x^T group slot), or None."""
+    def forward(ctx, x, wq, wk, wv, cos, sin, nh, nkv, causal, out_hint=None, doc_bounds=None):
+        """out_hint: the out-projection reading O (wgrad_operands.Proj: O^T into its x^T group slot), or None.
+        doc_bounds: the document mask of packed rows (ops.doc_bounds), or None."""
         _need(x, "x")
         B, S, Hd = x.shape
         D = wq.shape[0] // nh
@@ -1350,8 +1412,10 @@ class _QKVRopeAttentionFn(torch.autograd.Function):
         scale = 1.0 / math.sqrt(D)
         # O^T for the out-projection's wgrad (TT form), written by the attention epilogue for free
         o_t = WO.xt_sink(out_hint, nh * D, B * S, x)
-        o, lse = attention_block_fwd(q, k, v, scale, causal, o_t=o_t, rope_q=(cos, sin) if fuse_q else None)
+        o, lse = attention_block_fwd(q, k, v, scale, causal, o_t=o_t, rope_q=(cos, sin) if fuse_q else None,
+                                     doc_bounds=doc_bounds)
         ctx.save_for_backward(WO.saved_input(x2, N, x), W, qkv, o, lse, cos, sin)
+        ctx.doc_bounds = doc_bounds  # an integer tensor that no gradient flows to; shared by every layer
         ctx.params = (wq, wk, wv)
         ctx.meta = (B, S, Hd, nh, nkv, D, causal, scale)
         return WO.attach_t(o.view(B, S, nh * D), o_t)
@@ -1373,19 +1437,23 @@ class _QKVRopeAttentionFn(torch.autograd.Function):
         fused = os.getenv("PICO_FUSE_ROPE_BWD", "1") != "0"
         _attention_bwd_into(do.reshape(B, S, nh, D), q, k, v, o, lse, scale, causal,
                             dheads[:, :, :nh], dheads[:, :, nh:nh + nkv], dheads[:, :, nh + nkv:],
-                            rope=(cos, sin) if fused else None)
+                            rope=(cos, sin) if fused else None, doc_bounds=ctx.doc_bounds)
         if not fused:
             dqk = dheads[:, :, : nh + nkv]
             _rope_launch(dqk, dqk, cos, sin, True)
         dx, (dwq, dwk, dwv) = dgrad_wgrad("qkv", dqkv, W, ctx.params, x2)
-        return dx.view(B, S, Hd), dwq, dwk, dwv, None, None, None, None, None, None
+        return dx.view(B, S, Hd), dwq, dwk, dwv, None, None, None, None, None, None, None
 
 
-def qkv_rope_attention(x, wq, wk, wv, cos, sin, num_heads, num_kv_heads, causal, out_hint=None):
-    """Fused attention block (projections + RoPE + flash attention); see _QKVRopeAttentionFn."""
+def qkv_rope_attention(x, wq, wk, wv, cos, sin, num_heads, num_kv_heads, causal, out_hint=None, doc_bounds=None):
+    """Fused attention block (projections + RoPE + flash attention); see _QKVRopeAttentionFn. doc_bounds
+    (ops.doc_bounds, int32 [2, B, S]): the document mask of packed rows; needs causal."""
     D = wq.shape[0] // num_heads
+    if doc_bounds is None:
+        return _QKVRopeAttentionFn.apply(x, wq, wk, wv, cos[:, : D // 2], sin[:, : D // 2], num_heads, num_kv_heads,
+                                         causal, out_hint)
     return _QKVRopeAttentionFn.apply(x, wq, wk, wv, cos[:, : D // 2], sin[:, : D // 2], num_heads, num_kv_heads,
-                                     causal, out_hint)
+                                     causal, out_hint, doc_bounds)
 
 
 def _check_rope_tables(cos, sin, D):
@@ -1395,10 +1463,13 @@ def _check_rope_tables(cos, sin, D):
         raise ValueError("attention rope: cos/sin must be [>= S, D/2] with unit column stride")
 
 
-def _attention_bwd_into(dout, q, k, v, o, lse, softmax_scale, causal, dq, dk, dv, rope=None):
+def _attention_bwd_into(dout, q, k, v, o, lse, softmax_scale, causal, dq, dk, dv, rope=None, doc_bounds=None):
     """attention backward writing into caller-provided (possibly strided) dq/dk/dv. rope = (cos, sin)
     ([>= S, D/2] bf16 tables): q and k were rotated before the forward; dq and dk come back rotated by
-    -theta (the RoPE backward fused into the dQ sum and the dK epilogue, PICO_ATTN_ROPE_BWD)."""
+    -theta (the RoPE backward fused into the dQ sum and the dK epilogue, PICO_ATTN_ROPE_BWD). doc_bounds: as in
+    attention_block_fwd."""
+    if doc_bounds is not None:
+        _check_doc_bounds(doc_bounds, q, k, causal, "_attention_bwd_into")
     if dout.stride(-1) != 1 or any(s_ % 8 for s_ in dout.stride()[:3]):
         dout = dout.contiguous()
     a = _attn_args(q, k, v, o, lse, softmax_scale, causal)
@@ -1413,10 +1484,7 @@ def _attention_bwd_into(dout, q, k, v, o, lse, softmax_scale, causal, dq, dk, dv
         _check_rope_tables(cos, sin, q.shape[3])
         a.flags |= _lib.ATTN_ROPE_BWD
         a.rope_cos, a.rope_sin, a.rope_stride = _lib.ptr(cos), _lib.ptr(sin), cos.stride(0)
-    lib = _lib.load()
-    ws = torch.empty(lib.pico_attn_bwd_workspace_bytes(ctypes.byref(a)), dtype=torch.uint8, device=q.device)
-    a.workspace = _lib.ptr(ws)
-    _lib.check(lib.pico_attn_bwd(ctypes.byref(a), _lib.stream_of(q)), "pico_attn_bwd")
+    _launch_attn_bwd(a, q, doc_bounds)
 
 
 # --------------------------------------------------------------------------------------------

@@ -27,6 +27,8 @@ CONFIGS = {
     "d128_full": (4, 1024, 16, 16, 128, False),
     "d128_s4096": (1, 4096, 16, 16, 128, True),
     "d128_gqa4": (4, 1024, 32, 8, 128, True),
+    "b4_s4096": (4, 4096, 32, 32, 64, True),        # packed long rows: the shapes of the --docs times in DESIGN.md §4n
+    "d128_b4_s4096": (4, 4096, 32, 32, 128, True),
 }
 
 
@@ -38,12 +40,24 @@ def main():
                     help="q / k / v as strided views of one [B, S, (Hq + 2 Hkv) D] buffer (the training step's layout)")
     ap.add_argument("--cold", action="store_true",
                     help="overwrite a 1-GiB buffer before every iteration (the inputs leave L2 and the Infinity Cache)")
+    ap.add_argument("--docs", type=int, default=0,
+                    help="N > 0: the document-masked launch (causal configs) with every row packed from N equal "
+                         "documents; TFLOP/s then count the FLOPs of the N diagonal blocks (DESIGN.md §4n)")
     args = ap.parse_args()
     from picotron_amd import _lib as L
     from picotron_amd import ops
     L.load()
+    attn_fwd, attn_bwd = ops.attention_block_fwd, ops.attention_block_bwd
     for name in args.configs.split(","):
         B, S, Hq, Hkv, D, causal = CONFIGS[name]
+        if args.docs:
+            if not causal or S % args.docs:
+                raise SystemExit(f"--docs {args.docs}: {name} must be causal with S a multiple of the document count")
+            n = S // args.docs
+            start = (torch.arange(S, device="cuda", dtype=torch.int32) // n * n).expand(B, S).contiguous()
+            bounds = ops.doc_bounds(start)
+            attn_fwd = lambda *a, _b=bounds: ops.attention_block_fwd(*a, doc_bounds=_b)
+            attn_bwd = lambda *a, _b=bounds: ops.attention_block_bwd(*a, doc_bounds=_b)
         torch.manual_seed(0)
         if args.strided:
             qkv = torch.randn(B, S, Hq + 2 * Hkv, D, dtype=torch.bfloat16, device="cuda")
@@ -55,8 +69,8 @@ def main():
         do = torch.randn(B, S, Hq, D, dtype=torch.bfloat16, device="cuda")
         sc = 1 / math.sqrt(D)
         for _ in range(3):
-            o, lse = ops.attention_block_fwd(q, k, v, sc, causal)
-            ops.attention_block_bwd(do, q, k, v, o, lse, sc, causal)
+            o, lse = attn_fwd(q, k, v, sc, causal)
+            attn_bwd(do, q, k, v, o, lse, sc, causal)
         torch.cuda.synchronize()
         ids = [L.K_ATTN_FWD, L.K_ATTN_BWD_DKV, L.K_ATTN_BWD_Q,
                L.K_ATTN_BWD_KV]
@@ -66,19 +80,19 @@ def main():
         for _ in range(args.iters):
             if flush is not None:
                 flush.fill_(1.0)
-            o, lse = ops.attention_block_fwd(q, k, v, sc, causal)
+            o, lse = attn_fwd(q, k, v, sc, causal)
             if flush is not None:
                 flush.fill_(2.0)
-            ops.attention_block_bwd(do, q, k, v, o, lse, sc, causal)
+            attn_bwd(do, q, k, v, o, lse, sc, causal)
         torch.cuda.synchronize()
-        fl = 4.0 * B * Hq * S * S * D * (0.5 if causal else 1.0)
-        res = {"config": name, "strided": args.strided, "cold": args.cold, "B": B, "S": S, "Hq": Hq, "Hkv": Hkv, "D": D, "causal": causal}
+        fl = 4.0 * B * Hq * S * S * D * (0.5 if causal else 1.0) / max(args.docs, 1)
+        res = {"config": name, "docs": args.docs, "strided": args.strided, "cold": args.cold, "B": B, "S": S, "Hq": Hq, "Hkv": Hkv, "D": D, "causal": causal}
         # wall time of the whole backward call on the caller's stream (kernel timers off): the dQ and dK/dV
         # kernels plus the launch gaps between them
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(args.iters):
-            ops.attention_block_bwd(do, q, k, v, o, lse, sc, causal)
+            attn_bwd(do, q, k, v, o, lse, sc, causal)
         e1.record()
         torch.cuda.synchronize()
         res["bwd_wall_us"] = round(1e3 * e0.elapsed_time(e1) / args.iters, 2)
